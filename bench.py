@@ -1,6 +1,6 @@
 """Benchmark: scan-pair registrations/s (8k-pt clouds, 20 ICP iterations) at 1..N GPUs.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
 
 With ``--gpus N > 1`` and no ``WORLD_SIZE`` in the environment, bench.py starts
@@ -17,7 +17,17 @@ RCCL.  Inputs are resident in HBM before timing.  value = pairs registered by al
 ranks wall time.  The results checked (status, iterations, pairs of every rank and both pair groups
 against the oracle) are the TIMED run's, copied before any diagnostic rerun.
 
-Beside the headline: ``incl_upload`` (the same steps with each batch's H2D upload from pinned host
+A plain run sets up, warms up, times the K steps and prints the headline line (``value``,
+``ms_per_step``, the plan, ``batch_device_ms`` and the statuses / iteration counts of the timed
+rows); nothing else runs.  ``--dump-outputs DIR`` also writes the rows the last timed step produced
+(every rank's pairs in global order: what a caller of ``icp4r_align_batch_device`` and the gather
+receives) as ``DIR/<field>.npy``: ``T`` (pairs, 4, 4) float32, ``fitness`` float64 and the integer
+fields as float64.  The inputs are seeded (pair i from 1000 + i), so two builds run with the same
+arguments are comparable row for row.
+
+Every other leg runs only with ``--full``, after the timed steps and the dump, and adds its keys
+to the same line.  With ``--full``, beside the headline:
+``incl_upload`` (the same steps with each batch's H2D upload from pinned host
 memory inside the timed region, overlapped with the previous batch on a copy stream), ``gather``
 (the all-gather timed alone), ``roofline`` (the kernel with the larger share of the single-group
 step, the batched update since round 4, with the batched search beside it as ``nn_kernel``: SURVEY
@@ -62,6 +72,12 @@ def parse(argv=None):
     ap.add_argument("--pairs", type=int, default=1024, help="pairs per GPU")
     ap.add_argument("--points", type=int, default=8192)
     ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg: incl-upload, the all-gather alone, the "
+                         "per-kernel rooflines, the single-pair configs, the oracle checks and the CPU baselines "
+                         "(the options below choose among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the result rows of the last timed step to DIR/<field>.npy (rank 0, every rank's pairs)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="single-core CPU-baseline budget (rank 0, N=1)")
     ap.add_argument("--cpu-all-seconds", type=float, default=8.0, help="all-cores CPU-baseline budget")
     ap.add_argument("--no-cpu", action="store_true")
@@ -81,7 +97,12 @@ def parse(argv=None):
                     help="plan option for the library context (icp4r_set_plan_option; A/B runs, DESIGN.md §6)")
     ap.add_argument("--plan-from-env", action="store_true",
                     help="(tools) also take plan options from ICP4R_<NAME> environment variables")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.no_c3 and not args.full:
+        ap.error("--no-c3 reports the single-pair configs alone, which run under --full")
+    return args
 
 
 # ------------------------------------------------------------------------------------------ launcher
@@ -527,6 +548,21 @@ def single_pair_configs(ctx, which: list[str], sha, cpu_s: float | None, check: 
     return out
 
 
+# ------------------------------------------------------------------------------------------ outputs
+def dump_outputs(folder: str, rows) -> None:
+    """The result rows a caller of the timed path receives (icp4r_result, 96 B per pair, global pair
+    order), one array per field: ``T.npy`` (pairs, 4, 4) float32, source -> target as the library
+    stores it turned row-major; ``fitness.npy`` float64; the integer fields as float64."""
+    import icp4r
+
+    res = np.frombuffer(rows.tobytes(), dtype=icp4r.RESULT_DTYPE)
+    os.makedirs(folder, exist_ok=True)
+    np.save(os.path.join(folder, "T.npy"), np.ascontiguousarray(res["T"].reshape(-1, 4, 4).transpose(0, 2, 1)))
+    np.save(os.path.join(folder, "fitness.npy"), np.ascontiguousarray(res["fitness"], dtype=np.float64))
+    for name in ("iterations", "converged", "status", "convergence_state", "n_correspondences"):
+        np.save(os.path.join(folder, name + ".npy"), res[name].astype(np.float64))
+
+
 # ------------------------------------------------------------------------------------------ GPU run
 def run_gpu(args) -> int:
     import torch
@@ -628,6 +664,53 @@ def run_gpu(args) -> int:
     batch_ms, _ = ctx.batch_time_ms()
     # the TIMED run's results (every step writes the same rows; copied before any rerun below)
     timed = (gathered if world > 1 else results).cpu().numpy().copy()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, timed)
+    plan = icp4r.plan(P, n, n, ctx=ctx)
+    res = np.frombuffer(timed.tobytes(), dtype=icp4r.RESULT_DTYPE)
+    diag = {"status_nonzero": int((res["status"] != 0).sum()), "iter_min": int(res["iterations"].min()),
+            "iter_max": int(res["iterations"].max()), "conv_states": sorted(set(int(v) for v in res["convergence_state"]))}
+    value = world * P * args.steps / elapsed
+
+    def headline() -> dict:
+        return {
+            "metric": _metric(),
+            "value": value,
+            "unit": "pairs/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": elapsed / args.steps * 1e3,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "fp32",
+            "data": "synthetic (seeded 4D-radar scan pairs, SURVEY.md App. B)",
+            "full": bool(args.full),
+            "config": {
+                "workload": f"C3/C4: {P} independent pairs per GPU, {n}/{n}-pt scans, {args.iters} ICP iterations "
+                            f"(fixed) + fitness pass, exact NN ({'kd-block pruned' if plan['pruned'] else 'brute force'}), "
+                            f"PCL numerics (bit-exact float restatement)",
+                "nn_plan": plan,
+                "pairs_per_gpu": P, "points": n, "iterations": args.iters,
+                "parallelism": f"pairs sharded over {world} rank(s), RCCL all-gather of results" if world > 1
+                else "1 GPU",
+            },
+        }
+
+    def finish() -> int:
+        if comm is not None:
+            comm.check()
+            comm.close()
+        ctx.close()
+        if world > 1:
+            dist.destroy_process_group()
+        return 0
+
+    if not args.full:  # the plain run: the headline of the timed steps and nothing else
+        if rank == 0:
+            print(json.dumps({**headline(), "batch_device_ms": batch_ms, "result_diag": diag}), flush=True)
+        return finish()
 
     # the all-gather alone
     gather_ms = None
@@ -722,7 +805,6 @@ def run_gpu(args) -> int:
     upd_ms, upd_launches = ctx.stage_time_ms(icp4r.STAGE_UPDATE)
     st = ctx.nn_stats()  # work the NN kernels performed in the single-group steps
     evals, tests = st["evaluations"], st["box_tests"]
-    plan = icp4r.plan(P, n, n, ctx=ctx)
     kernel = "nn_lds_kernel" if plan["lds"] else "nn_pruned_kernel" if plan["pruned"] else "nn_kernel"
 
     # the single-pair configs C1, C2, C5 (rank 0 at N=1: one GPU each; their CPU baselines too)
@@ -733,12 +815,9 @@ def run_gpu(args) -> int:
 
     # checks on the TIMED results: statuses, iteration counts, and pairs of every rank / both pair
     # groups against the oracle (rank 0 regenerates those pairs' inputs from their seeds)
-    res = np.frombuffer(timed.tobytes(), dtype=icp4r.RESULT_DTYPE)
     status_ok = bool((res["status"] == 0).all())
     iters_ok = bool((res["iterations"] == args.iters).all())
-    diag = {"status_nonzero": int((res["status"] != 0).sum()), "iter_min": int(res["iterations"].min()),
-            "iter_max": int(res["iterations"].max()), "conv_states": sorted(set(int(v) for v in res["convergence_state"])),
-            "single_group_rerun_equal": single_group_equal}
+    diag["single_group_rerun_equal"] = single_group_equal
     ok = status_ok and iters_ok and single_group_equal
     check = []
     if rank == 0 and args.check > 0:
@@ -762,8 +841,6 @@ def run_gpu(args) -> int:
         ok = ok and all(c["dt_m"] <= 1e-4 and c["dr_rad"] <= 1e-4 for c in check)
     ok = ok and all(c.get("bit_exact_vs_oracle", True) and c["status"] == 0 for c in configs.values())
 
-    total_pairs = world * P * args.steps
-    value = total_pairs / elapsed
     # the search kernel's own work: every evaluation except the test kernel's one per hit
     evals_per_launch = (evals - st["cache_hits"]) / max(nn_launches, 1)
     tests_per_launch = tests / max(nn_launches, 1)
@@ -838,27 +915,7 @@ def run_gpu(args) -> int:
         if world == 1 and not args.no_cpu:
             cpu = cpu_baseline(src_h, tgt_h, args.iters, args.cpu_seconds, args.cpu_all_seconds)
         line = {
-            "metric": _metric(),
-            "value": value,
-            "unit": "pairs/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "fp32",
-            "data": "synthetic (seeded 4D-radar scan pairs, SURVEY.md App. B)",
-            "config": {
-                "workload": f"C3/C4: {P} independent pairs per GPU, {n}/{n}-pt scans, {args.iters} ICP iterations "
-                            f"(fixed) + fitness pass, exact NN ({'kd-block pruned' if plan['pruned'] else 'brute force'}), "
-                            f"PCL numerics (bit-exact float restatement)",
-                "nn_plan": plan,
-                "pairs_per_gpu": P, "points": n, "iterations": args.iters,
-                "parallelism": f"pairs sharded over {world} rank(s), RCCL all-gather of results" if world > 1
-                else "1 GPU",
-            },
+            **headline(),
             "roofline": roofline,
             ("nn_kernel" if update_first else "update_kernel"): beside,
             "incl_upload": upload,
@@ -875,13 +932,7 @@ def run_gpu(args) -> int:
             "result_diag": diag,
         }
         print(json.dumps(line), flush=True)
-    if comm is not None:
-        comm.check()
-        comm.close()
-    ctx.close()
-    if world > 1:
-        dist.destroy_process_group()
-    return 0
+    return finish()
 
 
 def main(argv=None) -> int:

@@ -9,7 +9,7 @@ R=$1; shift
 mkdir -p gpurun_out
 for r in $(seq 1 "$R"); do
     for lib in "$@"; do
-        out=$(ICP4R_LIBRARY="$lib" timeout -k 10 120 python3 bench.py --plan-from-env --no-cpu --no-upload --configs= --check 2 --steps 20 \
+        out=$(ICP4R_LIBRARY="$lib" timeout -k 10 120 python3 bench.py --full --plan-from-env --no-cpu --no-upload --configs= --check 2 --steps 20 \
               2> gpurun_out/ab_err.log | grep '^{')
         rc=$?
         if [ $rc -ne 0 ]; then echo "ab: bench failed on $lib (rc=$rc)"; tail -5 gpurun_out/ab_err.log; exit 2; fi

@@ -9,7 +9,7 @@ mkdir -p gpurun_out
 for r in $(seq 1 "$R"); do
     for setting in "$@"; do
         envs=(); [ "$setting" != "-" ] && read -r -a envs <<< "$setting"
-        out=$(env "${envs[@]}" timeout -k 10 120 python3 bench.py --plan-from-env --no-cpu --no-upload --configs= --check 2 --steps 20 \
+        out=$(env "${envs[@]}" timeout -k 10 120 python3 bench.py --full --plan-from-env --no-cpu --no-upload --configs= --check 2 --steps 20 \
               2> gpurun_out/env_ab_err.log | grep '^{')
         rc=$?
         if [ $rc -ne 0 ]; then echo "env_ab: bench failed on '$setting' (rc=$rc)"; tail -5 gpurun_out/env_ab_err.log; exit 2; fi

@@ -18,7 +18,7 @@ run() {  # run <config> <dir-suffix> <rocprof args...>
     if [ "$cfg" = C3 ]; then
         args="--steps 3 --warmup 1 --no-cpu --check 0 --no-upload --configs="
     else
-        args="--no-c3 --no-cpu --check 0 --configs $cfg"
+        args="--full --no-c3 --no-cpu --check 0 --configs $cfg"
     fi
     ICP4R_GROUPS=1 timeout -k 10 300 rocprofv3 "$@" -d "gpurun_out/prof_${cfg}_$d" -o run --output-format csv -- \
         python3 bench.py --plan-from-env $args > "gpurun_out/prof_${cfg}_$d.log" 2>&1
