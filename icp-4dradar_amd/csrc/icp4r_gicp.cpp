@@ -139,6 +139,7 @@ int run_gicp(icp4r_ctx* ctx, const PairArgs& a, int npairs, int max_n, int max_m
     if ((rc = setup_work(ctx, pl, npairs, max_n, idx_m, false, st, w))) return rc;
     const int64_t xs = w.x_stride;
     const int64_t ts = mm;
+    ctx->gicp_last_pairs = 0;  // (set again once both covariance passes are queued)
     HIP_TRY(ctx->gicp_gs.ensure((size_t)npairs * sizeof(GicpState)));
     HIP_TRY(ctx->gicp_cov_src.ensure((size_t)npairs * xs * 6 * sizeof(double)));
     HIP_TRY(ctx->gicp_cov_tgt.ensure((size_t)npairs * ts * 6 * sizeof(double)));
@@ -246,6 +247,9 @@ int run_gicp(icp4r_ctx* ctx, const PairArgs& a, int npairs, int max_n, int max_m
     }
     if (pl.pruned && brute) HIP_TRY(launch_index(a, w, npairs, st));
     if (kev) HIP_TRY(hipEventRecord(ce->stop, st));
+    ctx->gicp_last_pairs = npairs;
+    ctx->gicp_last_xs = xs;
+    ctx->gicp_last_ts = ts;
     int32_t* active = static_cast<int32_t*>(ctx->gicp_active.p);
     if (!ctx->gicp_hflag) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&ctx->gicp_hflag), 2 * sizeof(int64_t), hipHostMallocCoherent));
     volatile int64_t* hf = ctx->gicp_hflag;
@@ -428,6 +432,7 @@ int icp4r_gicp_covariances(icp4r_ctx* ctx, const float* cloud, int32_t n, int32_
     HIP_TRY(ctx->src.ensure(hc.size() * sizeof(float)));
     HIP_TRY(ctx->src_off.ensure(16));
     HIP_TRY(ctx->src_n.ensure(16));
+    ctx->gicp_last_pairs = 0;  // (gicp_cov_src is reused: the last registration's are gone)
     HIP_TRY(ctx->gicp_cov_src.ensure((size_t)n * 6 * sizeof(double)));
     HIP_TRY(hipMemcpyAsync(ctx->src.p, hc.data(), hc.size() * sizeof(float), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(ctx->src_off.p, &zero64, 8, hipMemcpyHostToDevice, st));
@@ -452,6 +457,31 @@ int icp4r_gicp_covariances(icp4r_ctx* ctx, const float* cloud, int32_t n, int32_
     static const int idx[9] = {0, 1, 2, 1, 3, 4, 2, 4, 5};
     for (int32_t i = 0; i < n; ++i)
         for (int t = 0; t < 9; ++t) cov_out[(size_t)i * 9 + t] = h6[(size_t)i * 6 + idx[t]];
+    return ICP4R_OK;
+}
+
+// Internal test hook (not part of the public ABI in icp4r_gicp.h): the covariances the context's last
+// GICP registration computed for one of its pairs — which = 0 the source's (the source's own index, on
+// the aux stream), 1 the target's (the plan's index) — the first n of them as out[n][9], row-major 3x3.
+// Waits for the context's stream (a batch queued on another stream is the caller's to wait for).
+// ICP4R_E_INVALID when the last GICP call on the context was not a registration
+// (icp4r_gicp_covariances reuses the source's buffer), or pair / n lies outside what it ran on.
+int icp4r__test_gicp_covariances(icp4r_ctx* ctx, int32_t pair, int32_t which, int32_t n, double* out) {
+    if (!ctx || !out || (which != 0 && which != 1)) return fail(ICP4R_E_INVALID, "bad arguments");
+    if (ctx->gicp_last_pairs <= 0) return fail(ICP4R_E_INVALID, "no GICP registration ran last on this context");
+    const int64_t stride = which == 0 ? ctx->gicp_last_xs : ctx->gicp_last_ts;
+    if (pair < 0 || pair >= ctx->gicp_last_pairs)
+        return fail(ICP4R_E_INVALID, "pair %d outside [0, %d)", pair, ctx->gicp_last_pairs);
+    if (n < 1 || n > stride) return fail(ICP4R_E_INVALID, "n %d outside [1, %lld]", n, (long long)stride);
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    const icp4r_host::DevBuf& buf = which == 0 ? ctx->gicp_cov_src : ctx->gicp_cov_tgt;
+    std::vector<double> h6((size_t)n * 6);
+    HIP_TRY(hipMemcpy(h6.data(), static_cast<const double*>(buf.p) + (size_t)pair * stride * 6, h6.size() * sizeof(double),
+                      hipMemcpyDeviceToHost));
+    static const int idx[9] = {0, 1, 2, 1, 3, 4, 2, 4, 5};
+    for (int32_t i = 0; i < n; ++i)
+        for (int t = 0; t < 9; ++t) out[(size_t)i * 9 + t] = h6[(size_t)i * 6 + idx[t]];
     return ICP4R_OK;
 }
 

@@ -130,12 +130,13 @@ __device__ void gicp_regularize(const double* c, int reg, double* o) {
         for (int s = 0; s < 3; ++s) o[3 * r + s] = V[3 * r] * v[0] * V[3 * s] + V[3 * r + 1] * v[1] * V[3 * s + 1] + V[3 * r + 2] * v[2] * V[3 * s + 2];
 }
 
-// mean-centred covariance of the kk nearest neighbours (sorted keys), divided by k as
-// calculate_covariances does, regularised; out: the upper triangle (xx, xy, xz, yy, yz, zz)
-// (the index is clamped to the cloud: an unfilled slot can never address outside it)
+// mean-centred covariance of the kk nearest neighbours (sorted keys), divided by their number as
+// calculate_covariances does (kk = k; a cloud of fewer than k points: kk = n, the whole cloud, divided
+// by n — the rule of icp4r_gicp.h, as the oracle), regularised; out: the upper triangle (xx, xy, xz,
+// yy, yz, zz) (the index is clamped to the cloud: an unfilled slot can never address outside it)
 template <int K>
-__device__ __forceinline__ void gicp_cov_from_knn(const uint64_t (&best)[K], int kk, int k, int reg, const float4* c,
-                                                  int n, double* out) {
+__device__ __forceinline__ void gicp_cov_from_knn(const uint64_t (&best)[K], int kk, int reg, const float4* c, int n,
+                                                  double* out) {
     double mean[3] = {0.0, 0.0, 0.0};
 #pragma unroll
     for (int s = 0; s < K; ++s) {
@@ -157,7 +158,7 @@ __device__ __forceinline__ void gicp_cov_from_knn(const uint64_t (&best)[K], int
                 for (int t = 0; t < 3; ++t) cv[3 * r + t] += d[r] * d[t];
         }
     }
-    for (int t = 0; t < 9; ++t) cv[t] /= (double)k;
+    for (int t = 0; t < 9; ++t) cv[t] /= (double)kk;
     double o[9];
     gicp_regularize(cv, reg, o);
     out[0] = o[0];
@@ -233,7 +234,7 @@ __global__ __launch_bounds__(kCovWG) void gicp_cov_kernel(const float4* __restri
     }
     knn_merge_lanes<K, L>(best);
     if (sub != 0 || i >= n) return;
-    gicp_cov_from_knn<K>(best, min(k, n), k, reg, c, n, cov_out + ((int64_t)p * stride + i) * 6);
+    gicp_cov_from_knn<K>(best, min(k, n), reg, c, n, cov_out + ((int64_t)p * stride + i) * 6);
 }
 
 // Pruned exact k-NN over the cloud's own Morton index (index_kernel of the ICP core, built with the
@@ -413,7 +414,7 @@ __global__ __launch_bounds__(kCovWG) void gicp_knn_cov_kernel(const float4* __re
     knn_merge_lanes<K, L>(best);
     if (sub != 0 || base + qi >= n) return;
     const uint32_t oi = __float_as_uint(qv.w);
-    gicp_cov_from_knn<K>(best, min(k, n), k, reg, cloud + off[p], n, cov_out + ((int64_t)p * stride + oi) * 6);
+    gicp_cov_from_knn<K>(best, min(k, n), reg, cloud + off[p], n, cov_out + ((int64_t)p * stride + oi) * 6);
 }
 
 // ---- per-iteration update

@@ -120,4 +120,8 @@ struct icp4r_ctx {
     hipEvent_t gicp_fork = nullptr, gicp_join = nullptr;
     std::vector<icp4r_host::EventPair> gicp_events;  // covariance launches (the iterations time as UPDATE)
     size_t gicp_used = 0;
+    // the layout of gicp_cov_src / gicp_cov_tgt as the last registration left them (pairs, points per
+    // pair of each; 0 pairs: none, or overwritten since): icp4r__test_gicp_covariances reads them back
+    int gicp_last_pairs = 0;
+    int64_t gicp_last_xs = 0, gicp_last_ts = 0;
 };

@@ -48,6 +48,8 @@ def _lib():
         L.icp4r_gicp_align_batch_device.argtypes = [vp, C.POINTER(Batch), C.POINTER(GicpParams), vp, vp]
         L.icp4r_gicp_covariances.restype = C.c_int
         L.icp4r_gicp_covariances.argtypes = [vp, vp, i32, i32, i32, i32, vp]
+        L.icp4r__test_gicp_covariances.restype = C.c_int
+        L.icp4r__test_gicp_covariances.argtypes = [vp, i32, i32, i32, vp]
         _bound = True
     return L
 
@@ -93,6 +95,17 @@ def covariances(cloud, k: int = 20, regularization: int = REG_PLANE, ctx: Contex
     out = np.zeros((n, 3, 3), np.float64)
     _check(_lib().icp4r_gicp_covariances(ctx.handle, _ptr(c), n, cs, k, regularization, _ptr(out)),
            "icp4r_gicp_covariances")
+    return out
+
+
+def last_align_covariances(pair: int, which: int, n: int, ctx: Context | None = None) -> np.ndarray:
+    """Test hook (not in the public header): the covariances the context's last align / align_batch_device
+    computed for `pair` — which = 0 the source's, 1 the target's — the first n as (n, 3, 3) float64.
+    Raises ICP4R_E_INVALID when no registration ran last (covariances() invalidates the record) or
+    pair / n is out of range."""
+    ctx = ctx or default_context()
+    out = np.zeros((n, 3, 3), np.float64)
+    _check(_lib().icp4r__test_gicp_covariances(ctx.handle, pair, which, n, _ptr(out)), "icp4r__test_gicp_covariances")
     return out
 
 

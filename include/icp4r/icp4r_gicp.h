@@ -72,7 +72,10 @@ int icp4r_gicp_align(icp4r_ctx* ctx, const float* src, int32_t n, int32_t src_st
 int icp4r_gicp_align_batch_device(icp4r_ctx* ctx, const icp4r_batch* batch, const icp4r_gicp_params* params,
                                   icp4r_result* results, void* hip_stream);
 
-/* FastGICP::calculate_covariances for one cloud (host buffers): cov_out[n][9] row-major 3x3. */
+/* FastGICP::calculate_covariances for one cloud (host buffers): cov_out[n][9] row-major 3x3.
+ * A cloud of n < k points (here and inside align): fast_gicp's expression reads neighbour columns it
+ * never filled, so the reference defines nothing; the rule here is that the neighbour set is the whole
+ * cloud and the divisor its size, cov = N Nᵀ / n before the regularisation (oracle/gicp_oracle.h). */
 int icp4r_gicp_covariances(icp4r_ctx* ctx, const float* cloud, int32_t n, int32_t stride_bytes, int32_t k,
                            int32_t regularization, double* cov_out);
 

@@ -98,7 +98,7 @@ static void inv3(const double* m, double* r) {
 
 /* FastGICP::calculate_covariances */
 void gicp_oracle_covariances(const float* cloud, int32_t n, int32_t k, int32_t reg, double* cov_out) {
-    if (k > n) k = n;
+    if (k > n) k = n; /* fewer than k points: the whole cloud is the neighbour set, divided by its size */
     float* bd = (float*)malloc(sizeof(float) * (size_t)(k > 0 ? k : 1));
     int* bi = (int*)malloc(sizeof(int) * (size_t)(k > 0 ? k : 1));
     for (int32_t i = 0; i < n; ++i) {
@@ -340,6 +340,7 @@ int gicp_oracle_align(const float* src, int32_t n, const float* tgt, int32_t m, 
     double* ct = (double*)malloc(sizeof(double) * 9 * (size_t)m);
     g.corr = (int32_t*)malloc(sizeof(int32_t) * (size_t)n);
     g.mah = (double*)malloc(sizeof(double) * 9 * (size_t)n);
+    for (int32_t i = 0; i < n; ++i) g.corr[i] = -1; /* max_iterations = 0: no linearisation, no correspondences */
     gicp_oracle_covariances(src, n, p->k, p->regularization, cs);
     gicp_oracle_covariances(tgt, m, p->k, p->regularization, ct);
     g.cs = cs;

@@ -50,7 +50,10 @@ typedef struct gicp_oracle_result {
 
 void gicp_oracle_params_default(gicp_oracle_params* p);
 
-/* calculate_covariances: cloud n x 4 floats (x, y, z, ·); cov_out n x 9 row-major. */
+/* calculate_covariances: cloud n x 4 floats (x, y, z, ·); cov_out n x 9 row-major.
+ * A cloud of n < k points: fast_gicp's expression reads neighbour columns it never filled, so the
+ * reference defines nothing; the project's rule (the same in include/icp4r/icp4r_gicp.h) is that the
+ * neighbour set is the whole cloud and the divisor its size, cov = N Nᵀ / n. */
 void gicp_oracle_covariances(const float* cloud, int32_t n, int32_t k, int32_t regularization, double* cov_out);
 
 /* FastGICP align from the identity or guess (row-major 4x4 double, may be NULL). */

@@ -8,6 +8,14 @@ of analytic clouds, independent numpy covariances, and pairs with a known rigid 
 (GPU vs oracle): covariances within 1e-9 relative (same double arithmetic; the k-NN sets identical);
 poses within 1e-5 (rotation rad / translation m: the Gauss-Newton sums run in a different order);
 nr_iterations and hasConverged identical; the fitness within 1e-6 relative.
+
+A cloud of fewer than k points (the reference defines nothing: fast_gicp reads neighbour columns it
+never filled): the neighbour set is the whole cloud and the divisor its size, on the device and in the
+oracle (test_gpu_small_clouds_fewer_points_than_k, every regularisation).
+
+tests/test_gicp_paths.py applies the same bars to the branches this file does not reach: the k-NN walk
+of clouds past 8192 points, every list length, degenerate clouds, the covariances computed inside
+align (read back), batches past 8 pairs, a partial distance gate, LM failure and max_iterations = 0.
 """
 import numpy as np
 import pytest
@@ -201,11 +209,25 @@ def test_gpu_align_guess_gate_and_errors(gpu_ctx, oracle_mod):
 
 @pytest.mark.gpu
 def test_gpu_small_clouds_fewer_points_than_k(gpu_ctx, oracle_mod):
+    """Fewer points than k: the neighbour set is the whole cloud and the divisor its size (the rule of
+    icp4r_gicp.h; fast_gicp defines nothing here). NONE, MIN_EIG and FROBENIUS see the divisor;
+    NORMALIZED_MIN_EIG and PLANE are scale-free.
+    (Measured on the MI355X with the device dividing by k, as it did before this rule was stated: at
+    n = 12 the error against the oracle was 2.8e+02 for NONE and MIN_EIG and 3.1e-04 for FROBENIUS, bars
+    7.1e-07 and 1.9e-08 — these three failing at n = 2, 4 and 12, the two scale-free methods within
+    5e-16; dividing by n every case is within 6e-14.)"""
     gicp = _gicp()
     src, tgt, _ = _scene(7, 200)
     s, t = src[:12], tgt[:15]
     got = gicp.covariances(s, 20, 3, ctx=gpu_ctx)
     np.testing.assert_allclose(got, oracle_mod.gicp_covariances(s, 20, 3), rtol=1e-9, atol=1e-12)
+    for n in (1, 2, 4, 12):
+        for reg in (0, 1, 2, 3, 4):
+            got = gicp.covariances(src[:n], 20, reg, ctx=gpu_ctx)
+            want = oracle_mod.gicp_covariances(src[:n], 20, reg)
+            err = float(np.abs(got - want).max())
+            print(f"n={n} k=20 reg={reg}: |got - want|max = {err:.3e}, |want|max = {np.abs(want).max():.3e}")
+            assert err <= 1e-9 * max(1.0, float(np.abs(want).max())), (n, reg, err)
     r, _ = gicp.align(s, t, gicp.default_params(k_correspondences=20), ctx=gpu_ctx)
     o = oracle_mod.gicp_align(s, t, k=20)
     assert r.iterations == o["iterations"] and bool(r.converged) == o["converged"]
