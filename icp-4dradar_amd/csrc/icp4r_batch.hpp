@@ -38,7 +38,7 @@ enum PlanOpt : int {
     kOptPhaseTicks, kOptKd, kOptMortonMwg, kOptPart, kOptSrcOrder, kOptFuseSeed, kOptTileOwn, kOptTileDefer,
     kOptGroups, kOptSearchCuDiv, kOptFuseTest, kOptFuseOrder, kOptSumsTail, kOptWideUpdate, kOptGatherPadded,
     kOptGicpCovBrute, kOptFoldKeys, kOptGicpSpec, kOptGicpGrid, kOptGicpKnnLanes, kOptResUpdate, kOptHeldUpdate,
-    kOptFitXform, kOptCounters, kOptStageSel, kNumPlanOpts
+    kOptFitXform, kOptCounters, kOptStageSel, kOptLazyX, kNumPlanOpts
 };
 static_assert(kNumPlanOpts <= 64, "icp4r_ctx::plan_set is a 64-bit mask");
 extern const char* const kPlanOptNames[kNumPlanOpts];
@@ -59,7 +59,7 @@ int setup_work(icp4r_ctx* ctx, const Plan& pl, int npairs, int max_n, int max_m,
 // One NN pass over every pair the pass wants (timed with the context's NN events).
 int nn_pass(icp4r_ctx* ctx, const Plan& pl, const icp4r::PairArgs& a, const icp4r::WorkArgs& w, int npairs, int max_n,
             int fitness_pass, int first, hipStream_t st, int ncu = 0, int test_fused = 0, int pass = -1,
-            int ordered = 0);
+            int ordered = 0, int pending = 0);
 int next_event(std::vector<icp4r_host::EventPair>& v, size_t& used, icp4r_host::EventPair** out);
 
 }  // namespace icp4r_pipe

@@ -105,7 +105,7 @@ const char* const kPlanOptNames[kNumPlanOpts] = {
     "phase_ticks", "kd", "morton_mwg", "part", "src_order", "fuse_seed", "tile_own", "tile_defer",
     "groups", "search_cu_div", "fuse_test", "fuse_order", "sums_tail", "wide_update", "gather_padded",
     "gicp_cov_brute", "fold_keys", "gicp_spec", "gicp_grid", "gicp_knn_lanes", "res_update",
-    "held_update", "fit_xform", "counters", "stage_sel"};
+    "held_update", "fit_xform", "counters", "stage_sel", "lazy_x"};
 
 int opt(const icp4r_ctx* ctx, PlanOpt k, int dflt) {
     return (ctx && (ctx->plan_set >> k & 1ull)) ? ctx->plan_val[k] : dflt;
@@ -397,7 +397,7 @@ int setup_work(icp4r_ctx* ctx, const Plan& pl, int npairs, int max_n, int max_m,
 // One NN pass over every active pair, timed with events: the roofline's kernel is the batched
 // search (nn_lds_kernel) or, for the other plans, the NN launch itself.
 int nn_pass(icp4r_ctx* ctx, const Plan& pl, const PairArgs& a, const WorkArgs& w0, int npairs, int max_n,
-            int fitness_pass, int first, hipStream_t st, int ncu, int test_fused, int pass, int ordered) {
+            int fitness_pass, int first, hipStream_t st, int ncu, int test_fused, int pass, int ordered, int pending) {
     EventPair* ne;
     int r;
     WorkArgs w = w0;  // debug: the pass' own event slots (plan option phase_ticks = 1)
@@ -425,7 +425,7 @@ int nn_pass(icp4r_ctx* ctx, const Plan& pl, const PairArgs& a, const WorkArgs& w
             ev.test_stop = te->stop;
         }
         HIP_TRY(launch_nn_lds(a, w, npairs, max_n, fitness_pass, first, ncu > 0 ? ncu : ctx->ncu, st, ev, test_fused,
-                              ordered));
+                              ordered, pending));
         return ICP4R_OK;
     }
     if (pl.tile) {  // the events bracket nn_tile_kernel itself (not its seed / record kernels)
@@ -591,6 +591,14 @@ int run_pairs(icp4r_ctx* ctx, const PairArgs& a, int npairs, int max_n, int max_
                              a.kp.max_d2 >= FLT_MAX && opt(ctx, kOptResUpdate, kDefaultResUpdate) != 0)
                                 ? 1
                                 : 0;
+    // ... whose every second fused tail is silent (fold_update_kernel only: neither the Σs tail nor the
+    // on-chip form; plan option lazy_x = 0: every tail stores X and U): it stores neither the moved points
+    // nor their bounds, the next update forms T_pend * X itself and its tail stores both steps at once.
+    // The last tail — the one before the fitness pass — always stores, so silent and storing tails
+    // alternate backwards from it, and the search after a silent tail flags the points it re-writes.
+    const bool lazy = fuse && !wg[0].sums_tail && !wg[0].res_update && opt(ctx, kOptLazyX, kDefaultLazyX) != 0;
+    for (int g = 0; g < groups; ++g) wg[g].lazy_x = lazy ? 1 : 0;
+    auto silent_tail = [&](int it) { return lazy && it >= 0 && it + 1 < iters && ((iters - 2 - it) & 1) != 0; };
     const bool kev = ctx->kernel_timing;  // per-kernel events (icp4r_set_kernel_timing; nn_pass: the same)
     // at most one pair per CU: the update in one 1024-thread workgroup per pair, its sigma panels side
     // by side (plan option wide_update = 0: fold_update_kernel's 256 threads)
@@ -610,7 +618,7 @@ int run_pairs(icp4r_ctx* ctx, const PairArgs& a, int npairs, int max_n, int max_
         for (int g = 0; g < groups; ++g) {
             const int ncu_g = search_cu > 0 ? search_cu : ctx->ncu;
             if ((rc = nn_pass(ctx, pl, ag[g], wg[g], gn[g], mn, 0, it == 0, gs[g], search_cu, fuse && it > 0, it,
-                              ford && it > 0)))
+                              ford && it > 0, silent_tail(it - 1) ? 1 : 0)))
                 return rc;
             EventPair* ue = nullptr;
             if (kev) {
@@ -618,7 +626,8 @@ int run_pairs(icp4r_ctx* ctx, const PairArgs& a, int npairs, int max_n, int max_
                 HIP_TRY(hipEventRecord(ue->start, gs[g]));
             }
             HIP_TRY(launch_update(ag[g], wg[g], gn[g], mn, pcl && !pl.pruned, gs[g], fuse && it + 1 < iters,
-                                  ford && it + 1 < iters ? ncu_g : 0, wide));
+                                  ford && it + 1 < iters ? ncu_g : 0, wide, silent_tail(it) ? 1 : 0,
+                                  silent_tail(it - 1) ? 1 : 0));
             if (kev) HIP_TRY(hipEventRecord(ue->stop, gs[g]));
         }
     }
@@ -1120,7 +1129,7 @@ int icp4r_get_plan_option(const icp4r_ctx* ctx, const char* name, int32_t* value
             0 /*nn_q: per plan*/, kDefaultLeaf, 0 /*chunk_sb: auto*/, -1 /*nn_lds: auto*/, 1, 1, 0 /*tile_run: auto*/,
             -1 /*solo: auto*/, 0, 0, 3, 1, kDefaultPartSize, -1 /*src_order: per plan*/, 1, 1, 1, kDefaultGroups,
             0 /*search_cu_div: groups*/, 1, 1, 0, 1, 0, 0, 1, kGicpSpec, kGicpGrid,
-            0 /*gicp_knn_lanes: auto*/, kDefaultResUpdate, kDefaultHeldUpdate, 1, 0, kDefaultStageSel};
+            0 /*gicp_knn_lanes: auto*/, kDefaultResUpdate, kDefaultHeldUpdate, 1, 0, kDefaultStageSel, kDefaultLazyX};
         *value = dflt[k];
     }
     if (is_set) *is_set = set ? 1 : 0;

@@ -91,6 +91,13 @@ struct PairState {
     // they are valid for the next pass A, which then reads nn_t only
     float sum_s[3];
     int32_t sums_ok;
+    // Lazy source cloud (WorkArgs::lazy_x): a silent tail tested the pair at T_pend * X without storing
+    // the moved points or their bounds; pending = 1 until the next tail (or the pair's last update)
+    // stores them.  While pending, a point whose stored L (X.w) has its sign bit set was re-written by
+    // the search in between and is at the newer state already; every other point's stored (X, L, U) is
+    // the consistent triple of the older state.
+    float T_pend[16];
+    int32_t pending;
 };
 
 // NN result of one query: (float bits of d² << 32) | target index.  d² >= 0, so the unsigned order
@@ -164,6 +171,9 @@ struct WorkArgs {
                           // in the fillers' registers from pass A to pass B (plan option held_update)
     int32_t fit_xform;    // 1 (one-tile plan, no cache, no seeds): the fitness pass' nn_tile_kernel forms
                           // X := final * input itself (fitness_prep_kernel's work; plan option fit_xform)
+    int32_t lazy_x;       // 1 (batched plan, fused test, fold_update_kernel): every second fused tail is
+                          // silent — it stores neither X nor U; the next update forms T_pend * X itself and
+                          // its tail stores two steps at once (PairState::pending; plan option lazy_x)
     float4* nn_t;       // [npairs * x_stride] the NN target of X_i: xyz, .w = its sorted target position |
                         // the query's sorted position << 14 (nt_pack)
     float4* sq;         // [npairs * x_stride] the pass's miss list in the order the test found them: a
@@ -215,13 +225,16 @@ struct NNLdsEvents {
     hipEvent_t test_start = nullptr, test_stop = nullptr, search_start = nullptr, search_stop = nullptr;
 };
 // ordered: the previous fold_update_kernel built the work list (no nn_order_kernel launch)
+// pending: the pass follows a silent tail (WorkArgs::lazy_x) — a searched point is stored whole, its L flagged
 hipError_t launch_nn_lds(const PairArgs& a, const WorkArgs& w, int npairs, int max_n, int fitness_pass, int first,
-                         int ncu, hipStream_t st, const NNLdsEvents& ev, int test_fused = 0, int ordered = 0);
+                         int ncu, hipStream_t st, const NNLdsEvents& ev, int test_fused = 0, int ordered = 0,
+                         int pending = 0);
 constexpr int kLdsMaxTargets = 8192;  // nn_lds_kernel: whole target set in LDS
 constexpr int kLdsMinPairs = 256;     // ... used for batches of at least this many pairs
 constexpr int kLdsMaxSources = 1 << 14;  // ... with at most this many sources (14-bit index / position fields)
 constexpr int kResMaxN = 8192;            // fold_update_res_kernel: sources of at most this many points
 constexpr int kDefaultResUpdate = 0;      // ... plan option res_update's default
+constexpr int kDefaultLazyX = 1;          // fold_update_kernel: plan option lazy_x's default
 constexpr int kHeldMaxN = 10 * 896;       // fold_update_held_kernel: sources of at most this many points
 constexpr int kHeldSmallN = 3 * 704;      // ... its 3-record form (the 2k scans; 11 filler waves) up to this many
 constexpr int kDefaultHeldUpdate = 1;     // ... plan option held_update's default
@@ -231,7 +244,9 @@ constexpr int kSoloMaxN = 1024;           // solo_kernel by default for single p
 hipError_t launch_update(const PairArgs& a, const WorkArgs& w, int npairs, int max_n, bool need_corr,
                          hipStream_t st, int tail_test = 0,
                          int order_ncu = 0,  // > 0: the launch also builds the next pass's work list
-                         bool wide = false);
+                         bool wide = false,
+                         int silent = 0,     // 1 (WorkArgs::lazy_x): the fused tail stores neither X nor U
+                         int pending = 0);   // 1 (WorkArgs::lazy_x): the previous launch's tail was silent
 // solo_kernel: every iteration and the fitness pass of each pair in one workgroup (PCL numerics,
 // targets <= kLdsMaxTargets, sources <= kCacheMaxN; after launch_init and launch_index)
 hipError_t launch_solo(const PairArgs& a, const WorkArgs& w, int npairs, int max_n, int iters, hipStream_t st);

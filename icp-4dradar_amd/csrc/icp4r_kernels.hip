@@ -278,6 +278,7 @@ __global__ __launch_bounds__(kInitWG) void init_kernel(PairArgs a, WorkArgs w) {
         st.iterations = 0;
         st.ncorr = 0;
         st.sums_ok = big ? -1 : 0;
+        st.pending = 0;
         // counts above the batch's declared max_src_n / max_tgt_n would overrun the workspace strides
         const bool too_big = n > w.x_stride || (w.leaf > 0 && m > w.t_stride);
         if (m <= 0 || bad || too_big) {
@@ -1945,6 +1946,13 @@ __device__ __forceinline__ float2 move_lu(float2 lu, float ox, float oy, float o
     return make_float2(fmaxf((lu.x - d) * 0.999999f, 0.0f), (lu.y + d) * 1.000001f);
 }
 
+// Lazy source cloud (WorkArgs::lazy_x, PairState::pending): L is never negative (move_lu clamps at 0,
+// lu_from_sec scales a square root), so the sign bit of a stored L marks a point that the search
+// re-wrote after a silent tail — it is at the newer state already.  Every reader of a stored L takes
+// fabsf.
+constexpr uint32_t kLazyFlag = 0x80000000u;
+__device__ __forceinline__ bool l_flagged(float L) { return (__float_as_uint(L) & kLazyFlag) != 0u; }
+
 __device__ __forceinline__ bool cache_hit(float L, float dj2) {
     return L * L * (1.0f - kCacheMargin) > dj2 * (1.0f + kCacheMargin);
 }
@@ -2024,6 +2032,7 @@ __global__ __launch_bounds__(kTestWG) void nn_cache_test_kernel(PairArgs a, Work
     for (int e = 0; e < kTestPer; ++e) {
         const int i = i0 + e * kTestWG + tid;
         const bool valid = i < n;
+        v[e].w = fabsf(v[e].w);
         if (xform) {
             float4 o = v[e];
             xform_pt(T, v[e].x, v[e].y, v[e].z, o.x, o.y, o.z);  // PCL transformCloud, in place
@@ -2368,7 +2377,8 @@ template <bool CACHE>
 __device__ __forceinline__ void lds_runs(const LdsTile& sh, unsigned long long* bestl, uint32_t* secl, uint16_t* ring,
                                          const float4* qv, const uint2* qm, int nlist, int m, int nsb, const v4f isl,
                                          const v4f ish, const PairArgs& a, const WorkArgs& w, int p, int64_t xs0,
-                                         float4* X, NNKey* key, bool want_key, bool corr, RunStats& rs) {
+                                         float4* X, NNKey* key, bool want_key, bool corr, RunStats& rs,
+                                         uint32_t lflag = 0u) {  // (kLazyFlag in a pending pass: ORed into L)
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
@@ -2657,7 +2667,7 @@ __device__ __forceinline__ void lds_runs(const LdsTile& sh, unsigned long long* 
             if (want_key) st_sc<2>(&key[orig], ko);
             if (CACHE) {  // the update reads X, nn_t: no correspondence record
                 const float2 lu = lu_from_sec(__uint_as_float(secl[lane]));
-                st_v4<2>(&X[orig], make_float4(x, y, z, lu.x));  // .w = L
+                st_v4<2>(&X[orig], make_float4(x, y, z, __uint_as_float(__float_as_uint(lu.x) | lflag)));  // .w = L
                 st_sc<2>(&w.nn_u[xs0 + orig], lu.y);
                 st_v4<2>(&w.nn_t[xs0 + orig], make_float4(tl_x(t), tl_y(t), tl_z(t), nt_pack((int)tpos, spos)));
             } else if (corr) {
@@ -2700,8 +2710,12 @@ __device__ __forceinline__ void claim_item(const PairArgs& a, const WorkArgs& w,
 // CACHE: per searched query the exact second-nearest distance too, stored as the cached-neighbour
 // state: L in X_i.w, U in nn_u[i], the NN's coordinates in nn_t[i] with .w = its index | the query's
 // sorted position << 14 (nt_pack) — the position is what the next test flags a miss at.
+// pending (launch-uniform, WorkArgs::lazy_x): the pass follows a silent tail, so the stored X of the pair's
+// other points is one step behind — a searched point's L is stored with kLazyFlag (its coordinates, from
+// the query record, are the moved ones in every pass).
 template <bool CACHE>
-__global__ __launch_bounds__(kLdsWG) void nn_lds_kernel(PairArgs a, WorkArgs w, int fitness_pass, int first, int ranked) {
+__global__ __launch_bounds__(kLdsWG) void nn_lds_kernel(PairArgs a, WorkArgs w, int fitness_pass, int first, int ranked,
+                                                        int pending) {
     static_assert(kLdsQ == 1, "one query per lane");
     __shared__ LdsNN sh;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -2880,7 +2894,8 @@ incl = (int)wave_scan_incl((uint32_t)incl);  // (DPP)
         unsigned long long* bestl = sh.r.best[wave];
         uint32_t* secl = sh.sec[wave];
         uint16_t* ring = sh.items[wave];
-        lds_runs<CACHE>(tv, bestl, secl, ring, qv, qm, nlist, m, nsb, isl, ish, a, w, p, xs0, X, key, want_key, corr, rs);
+        lds_runs<CACHE>(tv, bestl, secl, ring, qv, qm, nlist, m, nsb, isl, ish, a, w, p, xs0, X, key, want_key, corr, rs,
+                        pending ? kLazyFlag : 0u);
 #if ICP4R_CLAIM_AHEAD
         // the first wave done claims the next item (sh.nx[(it + 1) & 1]: item it - 1's words, read by
         // every wave before this item's staging barrier)
@@ -3819,8 +3834,20 @@ __device__ __forceinline__ int pair_cache_test(const PairArgs& a, const WorkArgs
                                                 uint32_t* need, int32_t* pre, float4* lv, uint2* lm, int lcap,
                                                 int32_t* mcount, int32_t* wcnt, bool fitness, uint64_t* stamp = nullptr,
                                                 const TailFirst<kPer>* first = nullptr, float* stg = nullptr,
-                                                float* sums_out = nullptr, int32_t* sums_ok = nullptr) {
+                                                float* sums_out = nullptr, int32_t* sums_ok = nullptr,
+                                                const float* Tp = nullptr, bool silent = false) {
+    // Lazy source cloud (WorkArgs::lazy_x; both workgroup-uniform, the update's tail only):
+    //  silent: X', L', U' are formed and tested as ever but not stored — the caller records T as the
+    //          pair's T_pend; the stored triple of every point stays consistent at the older state.
+    //  Tp:     the pair is pending (the previous tail was silent, Tp = its T): an unflagged point is first
+    //          brought to the state that tail would have stored — Tp * X, the bounds moved by that step, the
+    //          very expressions it evaluated — a flagged one (re-written by the search since) is there
+    //          already; then this tail's own step, stored with a positive L.
     static_assert(!SUMS || (WG - 64) * kPer <= kSumRow - 4, "staging rows");
+    static_assert(!(FROM_SRC && SUMS), "the fitness pass folds no sums");
+    float Tq[16];
+#pragma unroll
+    for (int q = 0; q < 16; ++q) Tq[q] = (!FROM_SRC && !SUMS && Tp) ? uload(Tp + q) : 0.0f;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     constexpr int WW = SUMS ? WG - 64 : WG;  // threads that test
     const bool worker = !SUMS || wave >= 1;
@@ -3884,18 +3911,32 @@ __device__ __forceinline__ int pair_cache_test(const PairArgs& a, const WorkArgs
             const int i = i0 + e * WW + wt;
             const bool valid = i < n;
             float4 o = v[e];
+            float4 b = v[e];  // the point and its bounds before this step (.w = L)
+            b.w = fabsf(v[e].w);
+            float Ub = U[e];
+            if (!FROM_SRC && !SUMS && Tp) {
+                float qx, qy, qz;
+                xform_pt(Tq, b.x, b.y, b.z, qx, qy, qz);
+                const float2 Lq = move_lu(make_float2(b.w, Ub), b.x, b.y, b.z, qx, qy, qz);
+                const bool newer = l_flagged(v[e].w);
+                b.x = newer ? b.x : qx;
+                b.y = newer ? b.y : qy;
+                b.z = newer ? b.z : qz;
+                b.w = newer ? b.w : Lq.x;
+                Ub = newer ? Ub : Lq.y;
+            }
             if (FROM_SRC)
                 xform_pt(T, sv[e].x, sv[e].y, sv[e].z, o.x, o.y, o.z);  // final * input
             else
-                xform_pt(T, v[e].x, v[e].y, v[e].z, o.x, o.y, o.z);  // PCL transformCloud, in place
-            const float2 Lm = move_lu(make_float2(v[e].w, U[e]), v[e].x, v[e].y, v[e].z, o.x, o.y, o.z);
+                xform_pt(T, b.x, b.y, b.z, o.x, o.y, o.z);  // PCL transformCloud, in place
+            const float2 Lm = move_lu(make_float2(b.w, Ub), b.x, b.y, b.z, o.x, o.y, o.z);
             o.w = Lm.x;
             const float d2 = l2_simple(o.x, o.y, o.z, t[e].x, t[e].y, t[e].z);
             const bool hit = valid & cache_hit(Lm.x, d2);
             // (the fitness pass: no later pass reads the bounds, and X only for the aligned output —
             // the misses' search records carry their own coordinates)
-            if (valid && (!fitness || a.aligned)) st_v4<1>(&X[i], o);
-            if (valid && !fitness) st_sc<1>(&uu[i], Lm.y);
+            if (valid && (!fitness || a.aligned) && !silent) st_v4<1>(&X[i], o);
+            if (valid && !fitness && !silent) st_sc<1>(&uu[i], Lm.y);
             if (SUMS && valid) {
                 sg[e * WW + wt] = o.x;
                 sg[kSumRow + e * WW + wt] = o.y;
@@ -3990,7 +4031,25 @@ struct FoldIn {
     const NNKey* K = nullptr;
     const float4* TG = nullptr;
     float4* Cw = nullptr;
+    // lazy source cloud (the pair is pending, C null): the previous tail's transform, which it did not
+    // store — X_i is Tp * X[i] (the expression that tail would have stored) unless X[i].w carries
+    // kLazyFlag (the search re-wrote the point since: it is the moved one already)
+    const float* Tp = nullptr;
 };
+// X_i of a pending pair from its stored record (FoldIn::Tp).  The transform is loaded here, at its use
+// by a filler (scalar loads): held from the pass's start it stayed live through the fold waves' register
+// groups and spilled them.
+__device__ __forceinline__ void pend_pt(const float* Tp, float4& r0) {
+    float Tq[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) Tq[k] = uload(Tp + k);
+    float qx, qy, qz;
+    xform_pt(Tq, r0.x, r0.y, r0.z, qx, qy, qz);
+    const bool newer = l_flagged(r0.w);  // (selects per component: one of the whole records takes their addresses)
+    r0.x = newer ? r0.x : qx;
+    r0.y = newer ? r0.y : qy;
+    r0.z = newer ? r0.z : qz;
+}
 
 // A running exact sum of non-negative doubles that are widened floats: S in units of 2^E (E = the
 // lowest set bit's exponent over the nonzero terms so far), saturated at 2^53 — the argument of
@@ -4056,6 +4115,7 @@ __device__ __forceinline__ void fold_pass_a(const KParams& kp, const FoldIn& f, 
     };
     auto rec_fix = [&](float4& r0, float4& r1) {
         if (!f.C) {
+            if (f.Tp) pend_pt(f.Tp, r0);
             const float d2 = l2_simple(r0.x, r0.y, r0.z, r1.x, r1.y, r1.z);
             r0.w = weighted ? (float)huber_w(d2, kp.huber_delta) : 1.0f;
             r1.w = d2;
@@ -4291,6 +4351,7 @@ __device__ __forceinline__ void fold_pass_b(const KParams& kp, const FoldIn& f, 
     };
     auto rec_fix = [&](float4& r0, float4& r1) {
         if (!f.C) {
+            if (f.Tp) pend_pt(f.Tp, r0);
             const float d2 = l2_simple(r0.x, r0.y, r0.z, r1.x, r1.y, r1.z);
             r0.w = weighted ? (float)huber_w(d2, kp.huber_delta) : 1.0f;
             r1.w = d2;
@@ -4325,7 +4386,8 @@ __device__ __forceinline__ void fold_pass_b(const KParams& kp, const FoldIn& f, 
     };
     // every correspondence kept and unweighted (PCL's defaults): the products need no distance
     const bool plain = !weighted && cnt >= n;  // (nothing rejected in this iteration)
-    auto products_plain = [&](const float4& r0, const float4& r1, float (&pr)[9]) __attribute__((always_inline)) {
+    auto products_plain = [&](float4 r0, const float4& r1, float (&pr)[9]) __attribute__((always_inline)) {
+        if (f.Tp) pend_pt(f.Tp, r0);
         const float sv[3] = {r0.x - ms[0], r0.y - ms[1], r0.z - ms[2]};
         const float dv[3] = {r1.x - md[0], r1.y - md[1], r1.z - md[2]};
 #pragma unroll
@@ -4617,9 +4679,56 @@ __device__ __forceinline__ void fold_pass_b(const KParams& kp, const FoldIn& f, 
     if (f.tk) f.tk[3] = __builtin_amdgcn_s_memrealtime();
 }
 
+// A pending pair (WorkArgs::lazy_x) that no storing tail follows — it converged or failed in this update, or
+// no further iteration runs: the store its silent tail left out, made now.  An unflagged point becomes
+// Tp * X with the bounds moved (that tail's expressions), a flagged one only loses its flag, so the
+// pair's stored state is the one every tail storing would have left.
+template <int WG>
+__device__ __forceinline__ void flush_pending(const WorkArgs& w, int p, int n, const float* Tp) {
+    float Tq[16];
+#pragma unroll
+    for (int q = 0; q < 16; ++q) Tq[q] = uload(Tp + q);
+    const int64_t xs = (int64_t)p * w.x_stride;
+    float4* X = w.X + xs;
+    float* uu = w.nn_u + xs;
+    constexpr int kPer = 4;  // (every load of a round before its first store, as transform_pair)
+    for (int i0 = 0; i0 < n; i0 += WG * kPer) {
+        float4 v[kPer];
+        float U[kPer];
+#pragma unroll
+        for (int e = 0; e < kPer; ++e) {
+            const int i = min(i0 + e * WG + (int)threadIdx.x, n - 1);
+            v[e] = X[i];
+            U[e] = uu[i];
+        }
+#pragma unroll
+        for (int e = 0; e < kPer; ++e) {
+            const int i = i0 + e * WG + (int)threadIdx.x;
+            if (i >= n) break;
+            float4 q = v[e];
+            xform_pt(Tq, v[e].x, v[e].y, v[e].z, q.x, q.y, q.z);
+            const float2 Lq = move_lu(make_float2(v[e].w, U[e]), v[e].x, v[e].y, v[e].z, q.x, q.y, q.z);
+            q.w = Lq.x;
+            if (l_flagged(v[e].w)) {
+                v[e].w = fabsf(v[e].w);
+                X[i] = v[e];
+            } else {
+                X[i] = q;
+                uu[i] = Lq.y;
+            }
+        }
+    }
+}
+
 // The update of pair p; returns the pair's work in the next pass (its misses in the fused test; 0
 // when it is not searched again).
-__device__ __forceinline__ int fold_update_pair(const PairArgs& a, const WorkArgs& w, int tail_test, int p,
+// silent (launch-uniform, WorkArgs::lazy_x): this launch's fused tail stores neither X nor U — unless the
+// pair is pending already (never two silent tails in a row: one flag bit tells two states apart, not three).
+// PEND (WorkArgs::lazy_x): the launch follows a silent tail, so its active pairs are pending — whether
+// a pass is pending is launch-uniform (the host loop's parity), and as a template argument the other
+// launches compile to the code they had (the pending forms cost registers: scalar ones for T_pend).
+template <bool PEND>
+__device__ __forceinline__ int fold_update_pair(const PairArgs& a, const WorkArgs& w, int tail_test, int silent, int p,
                                                 FoldShared& sh) {
     PairState& st = w.state[p];
     if (st.phase != kPhaseActive) return 0;
@@ -4648,7 +4757,12 @@ __device__ __forceinline__ int fold_update_pair(const PairArgs& a, const WorkArg
 #else
 #define WG_TICK(k)
 #endif
-    const FoldIn fin{C, Xp, NT, n};
+    // lazy source cloud: the previous tail was silent — passes A and B form T_pend * X themselves
+    const bool lazy = w.lazy_x && w.nn_u && !C && !w.sums_tail;  // (launch-uniform)
+    // (PEND: every active pair of the launch is pending — the tails alternate, and a pair that stops is flushed)
+    const float* Tp = PEND ? st.T_pend : nullptr;
+    FoldIn fin{C, Xp, NT, n};
+    fin.Tp = Tp;
     // the previous tail folded this pass A's Σs (w.sums_tail: eligible registrations; the flag is the
     // pair's, set only by a tail that ran)
     const bool sums_tail = w.sums_tail && tail_test && w.nn_u && !C;  // (launch-uniform)
@@ -4676,6 +4790,10 @@ __device__ __forceinline__ int fold_update_pair(const PairArgs& a, const WorkArg
     __syncthreads();
     if (ticks) w.ticks[3] = __builtin_amdgcn_s_memrealtime();
     WG_TICK(3);
+    if (Tp && !(tail && sh.s.flag == 0)) {  // no tail follows to make the pending store
+        flush_pending<kFoldWG>(w, p, n, Tp);
+        if (tid == 0) st.pending = 0;
+    }
     if (sh.s.flag == 1) return 0;  // error: PCL breaks before transforming
     if (!w.defer_xform) transform_pair<kFoldWG>(w, p, n, sh.s.T_inc, w.seed_next && w.corr);
     // The next pass's cached-neighbour test, fused (tail_test: another iteration follows and the pair
@@ -4703,8 +4821,16 @@ __device__ __forceinline__ int fold_update_pair(const PairArgs& a, const WorkArg
                 a, w, p, n, T, need, pre, lv, lm, kFoldRecsSums, &sh.mcount, sh.cnt, false, stamp, nullptr, stg,
                 st.sum_s, &st.sums_ok);
         } else {
+            const bool quiet = lazy && silent && !Tp;
             nwork = pair_cache_test<kFoldWG, ICP4R_TAIL_PER, false>(a, w, p, n, T, need, pre, lv, lm, kFoldRecs,
-                                                                    &sh.mcount, sh.cnt, false, stamp, &tf);
+                                                                    &sh.mcount, sh.cnt, false, stamp, &tf, nullptr,
+                                                                    nullptr, nullptr, Tp, quiet);
+            if (quiet) {  // the transform this tail tested at and did not store
+                if (tid < 16) st.T_pend[tid] = sh.s.T_inc[tid];
+                if (tid == 0) st.pending = 1;
+            } else if (Tp && tid == 0) {
+                st.pending = 0;
+            }
         }
     }
     if (ticks) w.ticks[4] = __builtin_amdgcn_s_memrealtime();
@@ -4730,12 +4856,14 @@ __device__ __forceinline__ int fold_update_pair(const PairArgs& a, const WorkArg
 #ifndef ICP4R_UPD_OCC
 #define ICP4R_UPD_OCC 4  // (experiment) workgroups per CU of fold_update_kernel: 4, 3 or 2
 #endif
-__global__ __launch_bounds__(kFoldWG, ICP4R_UPD_OCC) void fold_update_kernel(PairArgs a, WorkArgs w, int tail_test, int order_ncu) {
+template <bool PEND>
+__global__ __launch_bounds__(kFoldWG, ICP4R_UPD_OCC) void fold_update_kernel(PairArgs a, WorkArgs w, int tail_test, int order_ncu,
+                                                                             int silent) {
     __shared__ FoldShared sh;
     __shared__ OrderShared osh;
     __shared__ int32_t last;
     const int p = xcd_remap(blockIdx.x, gridDim.x);
-    const int nwork = fold_update_pair(a, w, tail_test, p, sh);
+    const int nwork = fold_update_pair<PEND>(a, w, tail_test, silent, p, sh);
     if (order_ncu <= 0) return;
     if (threadIdx.x == 0) {
         __hip_atomic_store(w.owork + p, nwork, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -5875,7 +6003,7 @@ __global__ __launch_bounds__(kPrepWG) void fitness_prep_kernel(PairArgs a, WorkA
         }
         if (uu) {  // X still holds the last NN pass's points (a deferred transform never ran), .w = L
             const float4 old = X[i];
-            const float2 Lm = move_lu(make_float2(old.w, uu[i]), old.x, old.y, old.z, o.x, o.y, o.z);
+            const float2 Lm = move_lu(make_float2(fabsf(old.w), uu[i]), old.x, old.y, old.z, o.x, o.y, o.z);
             o.w = Lm.x;
             uu[i] = Lm.y;
         }
@@ -6463,7 +6591,7 @@ hipError_t launch_index_cloud(const PairArgs& a, const WorkArgs& w, int npairs, 
 }
 
 hipError_t launch_nn_lds(const PairArgs& a, const WorkArgs& w, int npairs, int max_n, int fitness_pass, int first,
-                         int ncu, hipStream_t st, const NNLdsEvents& ev, int test_fused, int ordered) {
+                         int ncu, hipStream_t st, const NNLdsEvents& ev, int test_fused, int ordered, int pending) {
     // (query records: source index and sorted position in kNtPosShift bits each, every mode)
     if (w.leaf != kLdsLeaf || w.t_stride > kLdsTargets || npairs <= 0 || max_n > (1 << kNtPosShift))
         return hipErrorInvalidValue;
@@ -6479,6 +6607,7 @@ hipError_t launch_nn_lds(const PairArgs& a, const WorkArgs& w, int npairs, int m
         if (ev.test_stop && (e = hipEventRecord(ev.test_stop, st)) != hipSuccess) return e;
     }
     if (ordered && (first || !cache || fitness_pass || !test_fused)) return hipErrorInvalidValue;
+    if (pending && (first || !cache || fitness_pass || !test_fused || !w.lazy_x)) return hipErrorInvalidValue;
     if (!ordered)
         hipLaunchKernelGGL(nn_order_kernel, dim3(1), dim3(kOrderWG), 0, st, a, w, npairs, fitness_pass,
                            (first || !cache) ? 1 : 0, ncu);
@@ -6486,9 +6615,9 @@ hipError_t launch_nn_lds(const PairArgs& a, const WorkArgs& w, int npairs, int m
     if (ev.search_start && (e = hipEventRecord(ev.search_start, st)) != hipSuccess) return e;
     if (cache)
         hipLaunchKernelGGL((nn_lds_kernel<true>), dim3(grid), dim3(kLdsWG), 0, st, a, w, fitness_pass, first,
-                           test_fused && !first ? 1 : 0);
+                           test_fused && !first ? 1 : 0, pending);
     else
-        hipLaunchKernelGGL((nn_lds_kernel<false>), dim3(grid), dim3(kLdsWG), 0, st, a, w, fitness_pass, first, 0);
+        hipLaunchKernelGGL((nn_lds_kernel<false>), dim3(grid), dim3(kLdsWG), 0, st, a, w, fitness_pass, first, 0, 0);
     if (ev.search_stop && (e = hipEventRecord(ev.search_stop, st)) != hipSuccess) return e;
     return hipGetLastError();
 }
@@ -6549,8 +6678,13 @@ hipError_t launch_nn_pruned(int q, int chunk_sb, int chunks, const PairArgs& a, 
 }
 
 hipError_t launch_update(const PairArgs& a, const WorkArgs& w, int npairs, int max_n, bool need_corr, hipStream_t st,
-                         int tail_test, int order_ncu, bool wide) {
+                         int tail_test, int order_ncu, bool wide, int silent, int pending) {
+    if (silent && pending) return hipErrorInvalidValue;  // (never two silent tails in a row)
     if (order_ncu > 0 && (!tail_test || !w.owork || !w.plist || !w.plist_n || !w.nn_u || a.kp.numerics != kNumericsPCL))
+        return hipErrorInvalidValue;
+    // (lazy_x: fold_update_kernel's fused tail only — no other update kernel knows a pending pair)
+    if (w.lazy_x && (wide || need_corr || w.corr || w.res_update || w.sums_tail || !w.nn_u || !w.defer_xform ||
+                     a.kp.numerics != kNumericsPCL))
         return hipErrorInvalidValue;
     if (a.kp.numerics == kNumericsPCL) {
         if (need_corr)
@@ -6565,10 +6699,14 @@ hipError_t launch_update(const PairArgs& a, const WorkArgs& w, int npairs, int m
                  a.kp.huber_delta == INFINITY && a.kp.max_d2 >= FLT_MAX &&
                  !w.sums_tail && (!tail_test || (w.sq && w.sm && w.need && w.miss_cnt)))
             hipLaunchKernelGGL(fold_update_res_kernel, dim3(npairs), dim3(kResWG), 0, st, a, w, tail_test, order_ncu);
-        else
-            hipLaunchKernelGGL(fold_update_kernel, dim3(npairs), dim3(kFoldWG),
+        else if (w.lazy_x && pending)
+            hipLaunchKernelGGL(fold_update_kernel<true>, dim3(npairs), dim3(kFoldWG),
                                ICP4R_UPD_OCC >= 4 ? 0 : (ICP4R_UPD_OCC == 3 ? 12000 : 20000), st, a, w, tail_test,
-                               order_ncu);
+                               order_ncu, 0);
+        else
+            hipLaunchKernelGGL(fold_update_kernel<false>, dim3(npairs), dim3(kFoldWG),
+                               ICP4R_UPD_OCC >= 4 ? 0 : (ICP4R_UPD_OCC == 3 ? 12000 : 20000), st, a, w, tail_test,
+                               order_ncu, (w.lazy_x && tail_test && silent) ? 1 : 0);
     } else {
         hipLaunchKernelGGL(update_f64_kernel, dim3(npairs), dim3(kUpdWG), 0, st, a, w);
     }

@@ -55,6 +55,7 @@ PLAN_OPTIONS = (
     "nn_q", "leaf", "chunk_sb", "nn_lds", "nn_cache", "nn_tile", "tile_run", "solo", "xpad", "phase_ticks", "kd",
     "morton_mwg", "part", "src_order", "fuse_seed", "tile_own", "tile_defer", "groups", "search_cu_div",
     "fuse_test", "fuse_order", "sums_tail", "wide_update", "gather_padded", "gicp_cov_brute", "fold_keys", "gicp_spec", "gicp_grid", "gicp_knn_lanes", "res_update", "held_update", "fit_xform", "counters", "stage_sel",
+    "lazy_x",
 )
 # include/icp4r/icp4r_ego.h (radar ego velocity and the scan parse; icp4r.ego)
 EGO_EXPORTED_SYMBOLS = [
@@ -404,10 +405,21 @@ def plan(npairs: int, max_src_n: int, max_tgt_n: int, nn_mode: int = NN_AUTO, nu
     info = PlanInfo()
     _check(load().icp4r_plan(ctx.handle if ctx is not None else None, npairs, max_src_n, max_tgt_n, nn_mode, numerics,
                              C.byref(info)), "icp4r_plan")
-    return {"pruned": bool(info.pruned), "lds": bool(info.lds), "cache": bool(info.cache), "q": info.q, "splits": info.splits,
-            "leaf": info.leaf, "nn_blocks": info.nn_blocks, "solo": bool(info.solo),
-            "wide_update": bool(info.wide_update), "res_update": bool(info.res_update),
-            "held_update": bool(info.held_update)}
+    out = {"pruned": bool(info.pruned), "lds": bool(info.lds), "cache": bool(info.cache), "q": info.q, "splits": info.splits,
+           "leaf": info.leaf, "nn_blocks": info.nn_blocks, "solo": bool(info.solo),
+           "wide_update": bool(info.wide_update), "res_update": bool(info.res_update),
+           "held_update": bool(info.held_update)}
+    # lazy_x (run_pairs' rule; icp4r_plan_info has no field for it): the batched plan's fused tail in
+    # fold_update_kernel — neither the on-chip update nor the tail that folds the next pass A's sums
+    octx = ctx if ctx is not None else Context(NO_DEVICE)
+    try:
+        on = {k: octx.get_plan_option(k)[0] != 0 for k in ("fuse_test", "sums_tail", "lazy_x")}
+    finally:
+        if ctx is None:
+            octx.close()
+    out["lazy_x"] = bool(out["lds"] and out["cache"] and numerics == NUMERICS_PCL and on["fuse_test"]
+                         and not on["sums_tail"] and not out["res_update"] and on["lazy_x"])
+    return out
 
 
 _default_ctx: Context | None = None

@@ -56,8 +56,13 @@ def stats(d: str) -> dict:
         with open(path) as f:
             for r in csv.DictReader(f):
                 k = short(r["Name"])
-                out[k] = {"avg_ns": float(r["AverageNs"]), "calls": int(r["Calls"]),
-                          "percentage": float(r.get("Percentage", "nan"))}
+                row = {"avg_ns": float(r["AverageNs"]), "calls": int(r["Calls"]),
+                       "percentage": float(r.get("Percentage", "nan"))}
+                if k in out:  # a template's instantiations (fold_update_kernel<false> / <true>): one row
+                    o, calls = out[k], out[k]["calls"] + row["calls"]
+                    row = {"avg_ns": (o["avg_ns"] * o["calls"] + row["avg_ns"] * row["calls"]) / max(calls, 1),
+                           "calls": calls, "percentage": o["percentage"] + row["percentage"]}
+                out[k] = row
     return out
 
 
