@@ -369,14 +369,7 @@ constexpr int kKdPer = kKdMaxN / kIdxWG;  // consecutive list positions per thre
 
 constexpr int kKdBins = 2048;             // counting-sort bins per axis (11-bit quantised coordinate)
 
-#ifndef ICP4R_FLAG32
-#define ICP4R_FLAG32 0  // kd levels: one dword per point flag instead of a byte (measured: no change)
-#endif
-#if ICP4R_FLAG32
-typedef uint32_t kd_flag_t;
-#else
-typedef uint8_t kd_flag_t;
-#endif
+typedef uint8_t kd_flag_t;  // kd levels: a byte per point flag (one dword per flag measured no change)
 struct KdShared {
     uint16_t L[3][kKdMaxN];  // per axis: the point indices, sorted by that axis inside every segment
     union {
@@ -779,10 +772,6 @@ __device__ void index_boxes(const WorkArgs& w, int p, int n) {
     }
 }
 
-#ifndef ICP4R_KD_KEYS
-#define ICP4R_KD_KEYS 1  // kd levels read the quantised keys from a scratch copy, not the points
-#endif
-
 // The source of pair p is ordered by its target's kd tree (src_order_kernel) rather than its own.
 __device__ __forceinline__ bool src_by_tgt_tree(const PairArgs& a, const WorkArgs& w, int p) {
     const int m = a.tgt_n[p];
@@ -814,9 +803,9 @@ __device__ __forceinline__ void index_cloud(IndexShared& shu, const PairArgs& a,
         if (kdn)
             for (int k = tid; k < kKdnStride; k += kIdxWG) kdn[k] = 0u;  // (kd_order syncs before writing)
         // the quantised keys' scratch (3 x kKdMaxN u16): the pair's query-record area, unused until
-        // the source order / first search writes it (compile-time ICP4R_KD_KEYS=0: the levels re-read the points)
+        // the source order / first search writes it; the kd levels read the keys from this copy, not the points
         // (targets only: a pair's source build may run beside it on the same area)
-        uint16_t* gk = (ICP4R_KD_KEYS && is_tgt && w.qv && (int64_t)w.x_stride * (int64_t)sizeof(float4) >= 3 * kKdMaxN * 2)
+        uint16_t* gk = (is_tgt && w.qv && (int64_t)w.x_stride * (int64_t)sizeof(float4) >= 3 * kKdMaxN * 2)
                            ? reinterpret_cast<uint16_t*>(w.qv + (int64_t)p * w.x_stride)
                            : nullptr;
         if (n <= kKdMaxN / 2)
@@ -1404,20 +1393,17 @@ __global__ __launch_bounds__(kSoWG) void src_order_kernel(PairArgs a, WorkArgs w
     src_order_pair(a, w, xcd_remap(blockIdx.x, gridDim.x), so);
 }
 
-#ifndef ICP4R_FUSE_SRC_ORDER
-#define ICP4R_FUSE_SRC_ORDER 1  // targets-only grids order the pair's source in the same workgroup
-#endif
 static_assert(sizeof(SoShared) <= sizeof(IndexShared) && kSoWG == kIdxWG, "the source order reuses the index build's workgroup");
 __global__ __launch_bounds__(kIdxWG, 4) void index_kernel(PairArgs a, WorkArgs w) {
     __shared__ IndexShared shu;
     // grid (pairs, 2): target and source of every pair; (pairs, 1): targets only, every source
-    // ordered by its target's tree — by this workgroup right after the build (ICP4R_FUSE_SRC_ORDER:
+    // ordered by its target's tree — by this workgroup right after the build (fused source order:
     // one launch and one kernel boundary fewer, the tree read back while it is in this XCD's L2)
     const int g = xcd_remap(blockIdx.x + gridDim.x * blockIdx.y, gridDim.x * gridDim.y);
     const int p = gridDim.y == 2 ? g >> 1 : g;
     const bool is_tgt = gridDim.y == 2 ? (g & 1) == 0 : true;
     index_cloud(shu, a, w, p, is_tgt);
-    if (ICP4R_FUSE_SRC_ORDER && gridDim.y == 1) {
+    if (gridDim.y == 1) {
         __syncthreads();  // the tree (kdn) and sorted targets written; the LDS free
         src_order_pair(a, w, p, *reinterpret_cast<SoShared*>(&shu));
     }
@@ -1807,16 +1793,11 @@ __device__ __forceinline__ void lds_block(const v4f* tl, int b, v4f (&cs)[16]) {
 // drain's (d², key) pair forms in the aligned register pair of the slot's first two words (d²
 // overwrites x, dead once dx is formed) — with the key last, every evaluation paid a v_mov to pair
 // them (a 64-bit VGPR operand must start on an even register).
-#ifndef ICP4R_TL_KEYFIRST
-#define ICP4R_TL_KEYFIRST 1
-#endif
-__device__ __forceinline__ v4f tl_slot(const v4f t, uint32_t k) {
-    return ICP4R_TL_KEYFIRST ? (v4f){__uint_as_float(k), t.x, t.y, t.z} : (v4f){t.x, t.y, t.z, __uint_as_float(k)};
-}
-__device__ __forceinline__ float tl_x(const v4f c) { return ICP4R_TL_KEYFIRST ? c.y : c.x; }
-__device__ __forceinline__ float tl_y(const v4f c) { return ICP4R_TL_KEYFIRST ? c.z : c.y; }
-__device__ __forceinline__ float tl_z(const v4f c) { return ICP4R_TL_KEYFIRST ? c.w : c.z; }
-__device__ __forceinline__ uint32_t tl_key(const v4f c) { return __float_as_uint(ICP4R_TL_KEYFIRST ? c.x : c.w); }
+__device__ __forceinline__ v4f tl_slot(const v4f t, uint32_t k) { return (v4f){__uint_as_float(k), t.x, t.y, t.z}; }
+__device__ __forceinline__ float tl_x(const v4f c) { return c.y; }
+__device__ __forceinline__ float tl_y(const v4f c) { return c.z; }
+__device__ __forceinline__ float tl_z(const v4f c) { return c.w; }
+__device__ __forceinline__ uint32_t tl_key(const v4f c) { return __float_as_uint(c.x); }
 
 // The second-smallest d² of a block after one more evaluation: s2 ≥ b (the current best's d²)
 // holds throughout, so min(s2, max(b, d)) — "d below the best: the old best; else min(s2, d)" —
@@ -1847,16 +1828,7 @@ __device__ __forceinline__ float box_lb(const v4f lo, const v4f hi, const float 
     return __builtin_fmaf(gz, gz, __builtin_fmaf(gy, gy, gx * gx));
 }
 
-#ifndef ICP4R_SKIP_SEED
-#define ICP4R_SKIP_SEED 1  // the lane's seed block (evaluated whole up front) is never queued again
-#endif
-#ifndef ICP4R_SB_EXPAND
-#define ICP4R_SB_EXPAND 1  // a reached superblock's blocks tested for the lanes that reach it only
-#endif
-#ifndef ICP4R_SB_BATCH
-#define ICP4R_SB_BATCH 1  // candidate superblocks tested together per traversal step
-#endif
-constexpr int kSbBatch = ICP4R_SB_BATCH;
+constexpr int kSbBatch = 1;  // candidate superblocks tested together per traversal step
 
 static_assert(kSbBatch >= 1 && kSbBatch <= 5, "six bits per superblock in a 32-bit pack");
 struct LdsNN {
@@ -1873,7 +1845,7 @@ struct LdsNN {
     uint32_t sec[kLdsWaves][64];                       // 4 KB: second-smallest d² bits (CACHE search)
     uint16_t items[kLdsWaves][kRing + 64];             // 6 KB: (query lane << 9) | block; + a spare slot per lane
     int32_t wsum[kLdsWaves];                           // staging: bitmap popcounts per wave
-    int32_t cur;                                       // the pair this workgroup works on
+    int32_t cur;                                       // (unused since claim-ahead; kept so the layout below is unchanged)
     unsigned long long selm[kLdsWaves];                // staging (reach_all): superblocks per wave's queries
     int32_t fin;                                       // (claim-ahead) waves done with their runs, all items
     int32_t nx[2][5];                                  // (claim-ahead) item k's {index, item, n, m, misses} in nx[k & 1]
@@ -1957,13 +1929,12 @@ __device__ __forceinline__ bool cache_hit(float L, float dj2) {
     return L * L * (1.0f - kCacheMargin) > dj2 * (1.0f + kCacheMargin);
 }
 
-template <int WT = 0>
 __device__ __forceinline__ void write_corr_t(const WorkArgs& w, const PairArgs& a, int p, int i, float sx, float sy,
                                              float sz, float d2, const float4 t) {
     float4* C = w.corr + ((int64_t)p * w.x_stride + i) * 2;
     const float wt = a.kp.huber_delta < INFINITY ? (float)huber_w(d2, a.kp.huber_delta) : 1.0f;
-    st_v4<WT>(C, make_float4(sx, sy, sz, wt));
-    st_v4<WT>(C + 1, make_float4(t.x, t.y, t.z, d2));
+    C[0] = make_float4(sx, sy, sz, wt);
+    C[1] = make_float4(t.x, t.y, t.z, d2);
 }
 
 // With the cached-neighbour state a pass's keys are read only by the finish kernel's fitness (the
@@ -2101,9 +2072,6 @@ constexpr int kOrderBuckets = 32;
 constexpr int kPartBits = 10;  // work item = pair << kPartBits | part (parts of >= 64 misses)
 static_assert(kCacheMaxN / 64 <= (1 << kPartBits), "part field");
 
-#ifndef ICP4R_ITEMS_PER_CU
-#define ICP4R_ITEMS_PER_CU 1  // the work list's target items per CU when heavy pairs are cut (round 6: 1 +0.6 % over 2; 3, 4 slower)
-#endif
 struct OrderShared {
     int32_t bcnt[kOrderBuckets], boff[kOrderBuckets];
     unsigned long long tot;
@@ -2148,7 +2116,7 @@ __device__ __forceinline__ void order_items_body(const PairArgs& a, const WorkAr
     // the few slowly converging pairs with thousands of misses spread over several CUs
     // (at least part_size, and large enough that the pass has about 2 items per CU: a part costs a
     // target staging, so only the heavy tail of a light pass is worth cutting)
-    constexpr unsigned long long kIpc = ICP4R_ITEMS_PER_CU;
+    constexpr unsigned long long kIpc = 1;  // the work list's target items per CU (round 6: 1 +0.6 % over 2; 3, 4 slower)
     const int ps = (!all && w.part_size > 0) ? max(w.part_size, (int)((tot_s + kIpc * ncu - 1) / (kIpc * ncu))) : (1 << 30);
     auto heavy_parts = [&](int c) { return (c + ps - 1) / ps; };
     auto heavy_size = [&](int c, int k) { return min(ps, c - k * ps); };
@@ -2415,7 +2383,6 @@ __device__ __forceinline__ void lds_runs(const LdsTile& sh, unsigned long long* 
                     // -1 on idle lanes (never queue work, never widen the coarse bound)
         const int seed_pos0 = __builtin_amdgcn_readfirstlane(pj);
         const int seed_blk = pj / kLdsLeaf;
-        [[maybe_unused]] const uint32_t lane9 = (uint32_t)lane << 9;  // ring item: query lane << 9 | block
         {
             // seed: the previous match (first pass: the target at the same relative position)
             // and the rest of its 16-target block, evaluated up front from LDS — tight initial
@@ -2527,7 +2494,6 @@ __device__ __forceinline__ void lds_runs(const LdsTile& sh, unsigned long long* 
         // the non-empty ones are queued.  A test may use a bound a drain has since tightened:
         // that only queues more work, never loses a target.
         const uint64_t ck1 = __builtin_readcyclecounter();
-#if ICP4R_SB_EXPAND
         // A superblock some lane may reach has its 8 blocks tested for those lanes only: the c
         // lanes that passed are compacted (ds_permute: rank k -> lane k), and each round rs.tests 8
         // of them against the 8 blocks at once — lane L takes passed lane r0 + L / 8 and block
@@ -2560,7 +2526,7 @@ __device__ __forceinline__ void lds_runs(const LdsTile& sh, unsigned long long* 
             // this lane's tag: its lane id, and its seed block if that lies in sb (never queued:
             // it was evaluated whole up front)
             const int rel = seed_blk - sb * kSuper;
-            const uint32_t tag = (uint32_t)lane | ((ICP4R_SKIP_SEED && (uint32_t)rel < (uint32_t)kSuper) ? (8u | (uint32_t)rel) << 6 : 0u);
+            const uint32_t tag = (uint32_t)lane | ((uint32_t)rel < (uint32_t)kSuper ? (8u | (uint32_t)rel) << 6 : 0u);
             const uint32_t rk = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
             // passed lanes go to lane rank, the others to distinct lanes >= c (no collisions)
             const uint32_t dst = lane_select(m, (uint32_t)c + (uint32_t)lane - rk, rk);
@@ -2590,72 +2556,6 @@ __device__ __forceinline__ void lds_runs(const LdsTile& sh, unsigned long long* 
             }
             }
         }
-#else
-        for (;;) {
-            uint32_t sbpack = 0, valid = 0;
-#pragma unroll
-            for (int j = 0; j < kSbBatch; ++j) {
-                const int sbj = next_sb();
-                if (sbj >= 0) {
-                    sbpack |= (uint32_t)sbj << (6 * j);
-                    valid |= 1u << j;
-                }
-            }
-            if (!valid) break;
-            uint32_t pass = 0;
-#pragma unroll
-            for (int j = 0; j < kSbBatch; ++j) {
-                const int sbj = (sbpack >> (6 * j)) & 63;
-                // the lanes that may reach this superblock (its box broadcast from LDS)
-                const auto* sbb = lds_vbase(&sh.sbx[sbj][0]);
-                if (__ballot(pt_lb(sbb, x, y, z) <= bnd) != 0) pass |= 1u << j;
-            }
-            pass &= valid;
-            const int nv = __builtin_popcount(valid);
-            rs.ev_sbv += nv;
-            rs.tests += 64 * nv;
-            for (; pass; pass &= pass - 1) {
-                const int sb = (sbpack >> (6 * __builtin_ctz(pass))) & 63;
-                ++rs.ev_sbp;
-                // the lane's seed block was evaluated whole up front: never queued again
-                const int rel = seed_blk - sb * kSuper;
-                uint64_t nmk[kSuper];
-#pragma unroll
-                for (int h = 0; h < kSuper; h += 4) {
-                    // 4 rows of 24 B from a multiple of 4 rows (16-B aligned): six ds_read_b128 at
-                    // immediate offsets from one VGPR base
-                    const auto* b4 = (const __attribute__((address_space(3))) v4f*)lds_vbase(&sh.bx[sb * kSuper + h][0]);
-                    v4f r4[6];
-#pragma unroll
-                    for (int i = 0; i < 6; ++i) r4[i] = b4[i];
-                    float bb[4][6];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-#pragma unroll
-                        for (int c = 0; c < 6; ++c) bb[j][c] = r4[(6 * j + c) >> 2][(6 * j + c) & 3];
-                    // (two ballots: a ballot of the '&&' went through a VGPR select, 3 VALU more)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        nmk[h + j] = __ballot(pt_lb(bb[j], x, y, z) <= bnd) & (ICP4R_SKIP_SEED ? __ballot(rel != h + j) : ~0ull);
-                }
-                rs.tests += 64 * kSuper;
-#pragma unroll
-                for (int k = 0; k < kSuper; ++k) {  // (unrolled: a rolled loop with one drain
-                    const uint64_t mask = nmk[k];  //  copy measured 9 % slower)
-                    if (mask == 0) continue;
-                    ++rs.ev_blk;
-                    // every lane writes (no exec-mask branch): lanes that do not need the block
-                    // write their own spare slot past the ring (the mask itself is the select)
-                    const uint32_t slot = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32),
-                                                                    __builtin_amdgcn_mbcnt_lo((uint32_t)mask, tail));
-                    const uint32_t at = lane_select(mask, (uint32_t)(kRing + lane), slot & (kRing - 1));
-                    ring[at] = (uint16_t)(lane9 | (uint32_t)(sb * kSuper + k));
-                    tail += (uint32_t)__builtin_popcountll(mask);
-                    if (tail - head >= 64) drain(64);
-                }
-            }
-        }
-#endif
         if (tail != head) drain(tail - head);
         const uint64_t ck2 = __builtin_readcyclecounter();
         // the winner's coordinates come from its LDS slot (the key carries its position)
@@ -2664,12 +2564,14 @@ __device__ __forceinline__ void lds_runs(const LdsTile& sh, unsigned long long* 
         const v4f t = sh.tl[lds_swz((int)tpos)];
         if (live) {
             const NNKey ko = make_key(key_d2(kb), lk_idx(kb));  // (d², original index): PCL's answer
-            if (want_key) st_sc<2>(&key[orig], ko);
+            if (want_key) key[orig] = ko;
             if (CACHE) {  // the update reads X, nn_t: no correspondence record
                 const float2 lu = lu_from_sec(__uint_as_float(secl[lane]));
-                st_v4<2>(&X[orig], make_float4(x, y, z, __uint_as_float(__float_as_uint(lu.x) | lflag)));  // .w = L
-                st_sc<2>(&w.nn_u[xs0 + orig], lu.y);
-                st_v4<2>(&w.nn_t[xs0 + orig], make_float4(tl_x(t), tl_y(t), tl_z(t), nt_pack((int)tpos, spos)));
+                float4* const xo = &X[orig];
+                *xo = make_float4(x, y, z, __uint_as_float(__float_as_uint(lu.x) | lflag));  // .w = L
+                w.nn_u[xs0 + orig] = lu.y;
+                float4* const to = &w.nn_t[xs0 + orig];
+                *to = make_float4(tl_x(t), tl_y(t), tl_z(t), nt_pack((int)tpos, spos));
             } else if (corr) {
                 write_corr_t(w, a, p, orig, x, y, z, key_d2(kb), make_float4(tl_x(t), tl_y(t), tl_z(t), 0.f));
             }
@@ -2681,14 +2583,11 @@ __device__ __forceinline__ void lds_runs(const LdsTile& sh, unsigned long long* 
     }
 }
 
-// Claim-ahead (ICP4R_CLAIM_AHEAD): the next work item's index, pair word, sizes and miss count are
+// Claim-ahead: the next work item's index, pair word, sizes and miss count are
 // fetched by lane 0 of the first wave of the workgroup to finish its runs of the current item —
 // three dependent round trips (the queue add, the list, the pair's sizes) that then overlap the
 // slower waves' runs instead of sitting between two items.  The claim is at most one item's runs
 // early (the list is heaviest first: the last items are the smallest).
-#ifndef ICP4R_CLAIM_AHEAD
-#define ICP4R_CLAIM_AHEAD 1
-#endif
 __device__ __forceinline__ void claim_item(const PairArgs& a, const WorkArgs& w, int npl, int32_t* nx) {
     const int idx = atomicAdd(w.queue, 1);
     int item = 0, n = 0, m = 0, mc = 0;
@@ -2728,7 +2627,6 @@ __global__ __launch_bounds__(kLdsWG) void nn_lds_kernel(PairArgs a, WorkArgs w, 
     // summed over the registration in ticks[16..26], and per pass in pass_ticks[0..10];
     // tools/experiments/nn_events.py): wave-uniform adds, stored once at the end
     RunStats rs;
-#if ICP4R_CLAIM_AHEAD
     if (tid == 0) {
         claim_item(a, w, npl, sh.nx[0]);
         sh.fin = 0;
@@ -2743,20 +2641,6 @@ __global__ __launch_bounds__(kLdsWG) void nn_lds_kernel(PairArgs a, WorkArgs w, 
         const int item = __builtin_amdgcn_readfirstlane(nx[1]);
         const int p = item >> kPartBits, part = item & ((1 << kPartBits) - 1);
         const int n = __builtin_amdgcn_readfirstlane(nx[2]), m = __builtin_amdgcn_readfirstlane(nx[3]);
-#else
-    for (;;) {
-        if (tid == 0) sh.cur = atomicAdd(w.queue, 1);
-        __syncthreads();
-        const int idx = sh.cur;
-        if (idx >= npl) break;  // uniform: every wave read the same sh.cur
-        // debug (plan option phase_ticks = 1): per-pair compaction / staging / search wall time, summed over
-        // the pairs of the launch into ticks[8..10], pairs in ticks[11]
-        const bool tk = w.ticks != nullptr && tid == 0;
-        uint64_t tk0 = tk ? __builtin_amdgcn_s_memrealtime() : 0, tk1 = tk0, tk2 = tk0;
-        const int item = w.plist[idx];
-        const int p = item >> kPartBits, part = item & ((1 << kPartBits) - 1);
-        const int n = uload(a.src_n + p), m = uload(a.tgt_n + p);
-#endif
         const int nb = (m + kLdsLeaf - 1) / kLdsLeaf, nsb = (nb + kSuper - 1) / kSuper;
         const int64_t xs0 = (int64_t)p * w.x_stride;
         float4* X = w.X + xs0;
@@ -2776,11 +2660,7 @@ __global__ __launch_bounds__(kLdsWG) void nn_lds_kernel(PairArgs a, WorkArgs w, 
         //    rank in the miss bitmap.  The update kernel clears the bitmap (other parts may still be
         //    reading it).
         int nlist;
-#if ICP4R_CLAIM_AHEAD
         const int mc = (CACHE && !first && ranked) ? __builtin_amdgcn_readfirstlane(nx[4]) : kMissUnranked;
-#else
-        const int mc = (CACHE && !first && ranked) ? uload(w.miss_cnt + p) : kMissUnranked;
-#endif
         bool sel = false;  // a small ranked item: stage the superblocks its queries can reach only
         if (!(mc & kMissUnranked)) {
             // the fused test put the pair's misses in rank order already (pair_cache_test)
@@ -2800,7 +2680,7 @@ __global__ __launch_bounds__(kLdsWG) void nn_lds_kernel(PairArgs a, WorkArgs w, 
             const uint32_t f = tid < nwords ? gneed[tid] : 0u;
             const int c = __builtin_popcount(f);
             int incl = c;
-incl = (int)wave_scan_incl((uint32_t)incl);  // (DPP)
+            incl = (int)wave_scan_incl((uint32_t)incl);  // (DPP)
             if (lane == 63) sh.wsum[wave] = incl;
             __syncthreads();
             int base = 0, total = 0;
@@ -2896,12 +2776,10 @@ incl = (int)wave_scan_incl((uint32_t)incl);  // (DPP)
         uint16_t* ring = sh.items[wave];
         lds_runs<CACHE>(tv, bestl, secl, ring, qv, qm, nlist, m, nsb, isl, ish, a, w, p, xs0, X, key, want_key, corr, rs,
                         pending ? kLazyFlag : 0u);
-#if ICP4R_CLAIM_AHEAD
         // the first wave done claims the next item (sh.nx[(it + 1) & 1]: item it - 1's words, read by
         // every wave before this item's staging barrier)
         if (lane == 0 && atomicAdd(&sh.fin, 1) == it * kLdsWaves) claim_item(a, w, npl, sh.nx[(it + 1) & 1]);
-#endif
-        __syncthreads();  // LDS (targets, per-wave state, sh.cur) is reused by the next pair
+        __syncthreads();  // LDS (targets, per-wave state) is reused by the next pair
         if (tk) {
             unsigned long long* tt = reinterpret_cast<unsigned long long*>(w.ticks);
             atomicAdd(tt + 8, (unsigned long long)(tk1 - tk0));
@@ -2964,9 +2842,6 @@ __global__ __launch_bounds__(kLdsWG) void nn_tile_kernel(PairArgs a, WorkArgs w,
     const bool own = first >= 0;  // (single tile: launched with gridDim.x == 1)
     const int tile = blockIdx.x, part = blockIdx.y, p = blockIdx.z;
     const unsigned long long tk_entry = w.pass_ticks ? __builtin_amdgcn_s_memrealtime() : 0;
-#if defined(ICP4R_DIAG_TILE) && ICP4R_DIAG_TILE == 1  // (timing diagnostic only: later passes do nothing — wrong results)
-    if (first == 0 && !fitness_pass) return;
-#endif
     const int phase = uload(&w.state[p].phase);
     if (fitness_pass ? (phase == kPhaseInvalid) : (phase != kPhaseActive)) return;
     const int n = uload(a.src_n + p), m = uload(a.tgt_n + p);
@@ -3035,7 +2910,7 @@ __global__ __launch_bounds__(kLdsWG) void nn_tile_kernel(PairArgs a, WorkArgs w,
 #pragma unroll
             for (int q = 0; q < 16; ++q) T[q] = uload(&w.state[p].final_T[q]);
             xform_pt(T, v.x, v.y, v.z, v.x, v.y, v.z);
-            if (live) st_v4<4>(w.X + xs0 + o, v);
+            if (live) w.X[xs0 + o] = v;
         }
         if (own && first == 0 && !fitness_pass && w.defer_xform) {
             // the previous update's transformCloud(T_inc), deferred to here (one read and write of X
@@ -3045,7 +2920,7 @@ __global__ __launch_bounds__(kLdsWG) void nn_tile_kernel(PairArgs a, WorkArgs w,
 #pragma unroll
             for (int q = 0; q < 16; ++q) T[q] = uload(&w.state[p].T_inc[q]);
             xform_pt(T, v.x, v.y, v.z, v.x, v.y, v.z);
-            if (live) st_v4<4>(w.X + xs0 + o, v);
+            if (live) w.X[xs0 + o] = v;
         }
         x = v.x;
         y = v.y;
@@ -3154,24 +3029,18 @@ __global__ __launch_bounds__(kLdsWG) void nn_tile_kernel(PairArgs a, WorkArgs w,
     if (tail != head) drain(tail - head);
     const NNKey kb = bestl[lane];
     if (tk0) tk[3] = __builtin_amdgcn_s_memrealtime();
-#if defined(ICP4R_DIAG_TILE) && ICP4R_DIAG_TILE == 2  // (timing diagnostic only: no result stores in later passes — wrong results)
-    if (first == 0 && !fitness_pass) {
-        if (lane == 0 && kb == 0x1234) key[0] = kb;  // (keeps the search from being optimised away)
-        return;
-    }
-#endif
     if (own) {
         // the seed target lies in the tile and its block's bound cannot prune it, so the winner is a
         // real LDS slot; the sentinel position (kb == init) is handled all the same
         const NNKey ko = kb < init ? make_key(key_d2(kb), lk_idx(kb)) : k0;
         if (live) {
-            st_sc<4>(key + o, ko);
+            key[o] = ko;
             if (w.corr != nullptr && !fitness_pass) {  // PCL numerics: the update's correspondence records
                 const float4 t = kb < init ? [&] {
                     const v4f c = sh.tl[lds_swz((int)lk_pos(kb))];
                     return make_float4(tl_x(c), tl_y(c), tl_z(c), 0.f);
                 }() : a.tgt[uload(a.tgt_off + p) + key_idx(k0)];
-                write_corr_t<4>(w, a, p, o, x, y, z, key_d2(ko), t);
+                write_corr_t(w, a, p, o, x, y, z, key_d2(ko), t);
             }
         }
     } else if (live && kb < init) {
@@ -3293,13 +3162,11 @@ __device__ __forceinline__ float fold_row(const float* f, int len, float acc) {
     return k < len ? fold_tail<float>(f + k, len - k, acc) : acc;
 }
 
-#ifndef ICP4R_FOLD_AHEAD
-#define ICP4R_FOLD_AHEAD 2  // groups of 32 floats in flight ahead of the adds (1 or 2)
-#endif
+constexpr int kFoldAhead = 2;  // groups of 32 floats in flight ahead of the adds (1 or 2)
 template <typename TAcc>
 __device__ __forceinline__ TAcc fold_seq(const float* f, int len, TAcc acc) {
     int k = 0;
-    if (ICP4R_FOLD_AHEAD >= 2 && len >= 96) {
+    if (kFoldAhead >= 2 && len >= 96) {
         // three register groups in rotation, two loads in flight while a group is summed: 6.4-6.7
         // cycles per dependent add on gfx950 vs 7.6-9.0 with one group ahead (tools/experiments/chain_bench.hip)
         float4 a[8], b[8], c[8];
@@ -3406,44 +3273,13 @@ __device__ __forceinline__ void fold_seq_switch(const float* f, int len, int xa,
     }
 }
 
-// Elements [lo, hi) (0 <= lo <= hi <= 32, wave-uniform) of the 32-float window g (16-B aligned), in
-// order: the window in one round trip, the adds behind scalar branches.
-template <typename TAcc>
-__device__ __forceinline__ TAcc fold_window(const float* g, int lo, int hi, TAcc acc) {
-    float4 v[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const float4*>(g + 4 * u);
-    lo = __builtin_amdgcn_readfirstlane(lo);
-    hi = __builtin_amdgcn_readfirstlane(hi);
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-        if (4 * u + 0 >= lo && 4 * u + 0 < hi) acc = acc + (TAcc)v[u].x;
-        if (4 * u + 1 >= lo && 4 * u + 1 < hi) acc = acc + (TAcc)v[u].y;
-        if (4 * u + 2 >= lo && 4 * u + 2 < hi) acc = acc + (TAcc)v[u].z;
-        if (4 * u + 3 >= lo && 4 * u + 3 < hi) acc = acc + (TAcc)v[u].w;
-    }
-    return acc;
-}
-
-// fold_seq over row[a, b) of a 16-B aligned LDS row (a, b wave-uniform): the partial 32-float windows
-// at either end in one round trip each, the whole windows between them by fold_seq.
-#ifndef ICP4R_SPAN_WINDOW
-#define ICP4R_SPAN_WINDOW 0
-#endif
+// fold_seq over row[a, b) of a 16-B aligned LDS row (a, b wave-uniform): up to 3 leading elements
+// until row + a is aligned, then fold_seq.
 template <typename TAcc>
 __device__ __forceinline__ TAcc fold_span(const float* row, int a, int b, TAcc acc) {
-    if (!ICP4R_SPAN_WINDOW) {  // up to 3 leading elements until row + a is aligned, then fold_seq
-        const int a4 = min(b, (a + 3) & ~3);
-        if (a < a4) acc = fold_tail<TAcc>(row + a, a4 - a, acc);
-        return a4 < b ? fold_seq<TAcc>(row + a4, b - a4, acc) : acc;
-    }
-    if (b <= a) return acc;
-    const int w0 = a & ~31;
-    if (b <= w0 + 32) return fold_window<TAcc>(row + w0, a - w0, b - w0, acc);
-    if (a > w0) acc = fold_window<TAcc>(row + w0, a - w0, 32, acc);
-    const int m0 = a > w0 ? w0 + 32 : w0, m1 = b & ~31;
-    if (m1 > m0) acc = fold_seq<TAcc>(row + m0, m1 - m0, acc);
-    return b > m1 ? fold_window<TAcc>(row + m1, 0, b - m1, acc) : acc;
+    const int a4 = min(b, (a + 3) & ~3);
+    if (a < a4) acc = fold_tail<TAcc>(row + a, a4 - a, acc);
+    return a4 < b ? fold_seq<TAcc>(row + a4, b - a4, acc) : acc;
 }
 
 // The double chains (PCL's MSE sum and getFitnessScore) over values the fillers stored as doubles:
@@ -3649,12 +3485,7 @@ __device__ __forceinline__ void transform_pair(const WorkArgs& w, int p, int n, 
     }
 }
 
-#ifndef ICP4R_TAIL_PER
-#define ICP4R_TAIL_PER 4  // fused test: points per thread per pipelined group
-#endif
-#ifndef ICP4R_TAIL_REV
-#define ICP4R_TAIL_REV 1  // fused test: the pair's point groups last to first
-#endif
+constexpr int kTailPer = 4;  // fused test: points per thread per pipelined group
 
 // ---------------------------------------------------------------------------------------------
 // The cached-neighbour test of one pair by one workgroup of WG threads (the update's fused tail, and
@@ -3686,7 +3517,7 @@ template <int WG, int kPer, bool SUMS = false>
 __device__ __forceinline__ int tail_group0(int n) {  // first (last-to-first) group's start
     constexpr int WW = SUMS ? WG - 64 : WG;
     const int kStep = WW * kPer, ngrp = (n + kStep - 1) / kStep;
-    return (ICP4R_TAIL_REV && !SUMS ? ngrp - 1 : 0) * kStep;
+    return (!SUMS ? ngrp - 1 : 0) * kStep;
 }
 template <int WG, int kPer, bool SUMS = false>
 __device__ __forceinline__ void tail_prefetch(const WorkArgs& w, int p, int n, TailFirst<kPer>& f) {
@@ -3704,29 +3535,21 @@ __device__ __forceinline__ void tail_prefetch(const WorkArgs& w, int p, int n, T
     }
 }
 
-// A fold wave's issue priority (ICP4R_FOLD_PRIO): its sequential chain is one dependent add after
+// A fold wave's issue priority: its sequential chain is one dependent add after
 // another, and the SIMD's other waves (fillers, the fused test's workers) otherwise take the issue
 // slots between them.
-#ifndef ICP4R_FOLD_PRIO
-#define ICP4R_FOLD_PRIO 1
-#endif
 __device__ __forceinline__ void fold_prio(bool hi) {
-    if (ICP4R_FOLD_PRIO) {
-        if (hi)
-            __builtin_amdgcn_s_setprio(3);
-        else
-            __builtin_amdgcn_s_setprio(0);
-    }
+    if (hi)
+        __builtin_amdgcn_s_setprio(3);
+    else
+        __builtin_amdgcn_s_setprio(0);
 }
 
 // SUMS (the update's tail, eligible pairs): the next pass A's Σs folded here, in index order, over the X
 // the test writes — wave 0 lanes 0..2 fold, waves 1.. test (groups of (WG - 64) * kPer points, first
 // to last, each group's new coordinates staged in `stg`: two buffers of 3 rows of kSumRow floats); the sums go to
 // sums_out[0..2] (the pair state) with *sums_ok = 1.
-#ifndef ICP4R_SUMS_PER
-#define ICP4R_SUMS_PER 2  // the Σs tail's points per worker and group (4: 185 vs 179.5 us per update)
-#endif
-constexpr int kSumPer = ICP4R_SUMS_PER;
+constexpr int kSumPer = 2;  // the Σs tail's points per worker and group (4: 185 vs 179.5 us per update)
 constexpr int kSumRow = 192 * kSumPer + 4;  // staged points per group (192 workers x kSumPer) + pad
 constexpr int kSumBuf = 3 * kSumRow;        // one group's staging; two alternate (double buffer)
 // The end of a pair's cached-neighbour test (pair_cache_test; res_update_pair's tail): the per-wave
@@ -3788,7 +3611,7 @@ __device__ __forceinline__ int test_place(const WorkArgs& w, int p, int n, int h
             sum += c[j];
         }
         int incl = sum;
-incl = (int)wave_scan_incl((uint32_t)incl);  // (DPP)
+        incl = (int)wave_scan_incl((uint32_t)incl);  // (DPP)
         int run = incl - sum;
 #pragma unroll
         for (int j = 0; j < kW; ++j) {
@@ -3807,12 +3630,13 @@ incl = (int)wave_scan_incl((uint32_t)incl);  // (DPP)
     };
     // (unconditional: a slot past the list re-read record tot - 1 and writes its very bytes to its
     // very rank again)
-    auto put = [&](const float4& r, const uint2& m) {
+    auto put = [&](const float4 r, const uint2& m) {
         const uint32_t sp = min(m.y, (uint32_t)(n - 1));
         const int rk = pre[sp >> 5] + __builtin_popcount(need[sp >> 5] & ((1u << (sp & 31)) - 1u));
-        st_v4<1>(&qv[rk], r);
+        qv[rk] = r;
         const uint2 mm = make_uint2((m.x & kNtIdxMask) | (sp << kNtPosShift), m.x >> kNtPosShift);
-        st_sc<1>(reinterpret_cast<uint64_t*>(&qm[rk]), (uint64_t)mm.x | ((uint64_t)mm.y << 32));
+        uint64_t* const qmk = reinterpret_cast<uint64_t*>(&qm[rk]);
+        *qmk = (uint64_t)mm.x | ((uint64_t)mm.y << 32);
     };
     for (int k0 = tid; k0 < tot; k0 += 4 * WG) {
         float4 r0, r1, r2, r3;  // (named, not an array: an array went to scratch)
@@ -3873,12 +3697,12 @@ __device__ __forceinline__ int pair_cache_test(const PairArgs& a, const WorkArgs
             if (FROM_SRC) ss[e] = src[i];
         }
     };
-    // Groups are visited last to first (ICP4R_TAIL_REV): the update's pass B has just streamed the
+    // Groups are visited last to first: the update's pass B has just streamed the
     // pair's X and nn_t front to back, so its most recently fetched lines — the ones still in the
     // L2 / MALL — are the pair's last ones.  (The folds must run in index order; the test may run in
     // any.)
     const int ngrp = (n + kStep - 1) / kStep;
-    auto grp0 = [&](int g) { return (ICP4R_TAIL_REV && !SUMS ? ngrp - 1 - g : g) * kStep; };
+    auto grp0 = [&](int g) { return (!SUMS ? ngrp - 1 - g : g) * kStep; };
     if (ngrp > 0 && worker) {
         if (first && !FROM_SRC) {
 #pragma unroll
@@ -3935,8 +3759,8 @@ __device__ __forceinline__ int pair_cache_test(const PairArgs& a, const WorkArgs
             const bool hit = valid & cache_hit(Lm.x, d2);
             // (the fitness pass: no later pass reads the bounds, and X only for the aligned output —
             // the misses' search records carry their own coordinates)
-            if (valid && (!fitness || a.aligned) && !silent) st_v4<1>(&X[i], o);
-            if (valid && !fitness && !silent) st_sc<1>(&uu[i], Lm.y);
+            if (valid && (!fitness || a.aligned) && !silent) X[i] = o;
+            if (valid && !fitness && !silent) uu[i] = Lm.y;
             if (SUMS && valid) {
                 sg[e * WW + wt] = o.x;
                 sg[kSumRow + e * WW + wt] = o.y;
@@ -3998,10 +3822,7 @@ constexpr int kFoldChunkP = 512;  // points per LDS chunk of the fold passes
 // Each fold chain's row is padded by kFoldPad floats: unpadded, rows 2 KB apart start on the same
 // LDS bank, and the 7-9 fold lanes' ds_read_b128 of one column were a 7-9-way bank conflict on every
 // read.  Padded by 16 B they take distinct banks.
-#ifndef ICP4R_FOLD_PAD
-#define ICP4R_FOLD_PAD 4
-#endif
-constexpr int kFoldPad = ICP4R_FOLD_PAD;
+constexpr int kFoldPad = 4;
 constexpr int kFoldRow = kFoldChunkP + kFoldPad;
 
 // the fused test's LDS miss records (24 B each) after the bitmap and its prefixes, in the fold buffers
@@ -4086,10 +3907,7 @@ __device__ __forceinline__ void wave_exact_total(uint64_t& S, int& E) {  // ever
 }
 
 constexpr int kSliceGroup = 14;  // panels folded together (9 x 14 = 126 chains: two fold waves)
-#ifndef ICP4R_FILL_BATCH
-#define ICP4R_FILL_BATCH 2
-#endif
-constexpr int kFillBatch = ICP4R_FILL_BATCH;  // a filler's correspondences in flight per round
+constexpr int kFillBatch = 2;  // a filler's correspondences in flight per round
 
 // Pass A of the PCL-numerics update by a workgroup of WG threads over LDS chunks of CH points
 // (buf: two chunks of 9 rows of ROW floats): wave 0 lanes 0..6 fold Σs, Σd (Eigen 3.3
@@ -4452,11 +4270,7 @@ __device__ __forceinline__ void fold_pass_b(const KParams& kp, const FoldIn& f, 
 #pragma unroll
                 for (int e = 0; e < kPerB; ++e) {
                     const int i = ch.c0 + min(tid - 64 + e * kFillB, ch.len - 1);
-#ifdef ICP4R_DIAG_REVB  // (timing diagnostic only: pass B reads the points last to first — wrong results)
-                    rec(n - 1 - i, r[e][0], r[e][1]);
-#else
                     rec(i, r[e][0], r[e][1]);
-#endif
                 }
             };
             auto store_b = [&](int c, const Chunk& ch, float4 (&r)[kPerB][2]) __attribute__((always_inline)) {
@@ -4777,12 +4591,12 @@ __device__ __forceinline__ int fold_update_pair(const PairArgs& a, const WorkArg
     // the fused test's first point group is loaded, and its LDS bitmap cleared, while thread 0 solves
     const bool tail = tail_test && w.nn_u;
     int nwork = 0;
-    TailFirst<ICP4R_TAIL_PER> tf;
+    TailFirst<kTailPer> tf;
     uint32_t* need = reinterpret_cast<uint32_t*>(&sh.buf[0][0][0]);  // the fold buffers are free now
     if (tail) {
         // (the Σs-folding tail loads its first group itself: a second prefetch layout held across the
         // solve spilled to scratch)
-        if (!sums_tail) tail_prefetch<kFoldWG, ICP4R_TAIL_PER>(w, p, n, tf);
+        if (!sums_tail) tail_prefetch<kFoldWG, kTailPer>(w, p, n, tf);
         for (int k = tid; k < ((n + 31) >> 5); k += kFoldWG) need[k] = 0u;
         if (tid == 0) sh.mcount = 0;
     }
@@ -4822,7 +4636,7 @@ __device__ __forceinline__ int fold_update_pair(const PairArgs& a, const WorkArg
                 st.sum_s, &st.sums_ok);
         } else {
             const bool quiet = lazy && silent && !Tp;
-            nwork = pair_cache_test<kFoldWG, ICP4R_TAIL_PER, false>(a, w, p, n, T, need, pre, lv, lm, kFoldRecs,
+            nwork = pair_cache_test<kFoldWG, kTailPer, false>(a, w, p, n, T, need, pre, lv, lm, kFoldRecs,
                                                                     &sh.mcount, sh.cnt, false, stamp, &tf, nullptr,
                                                                     nullptr, nullptr, Tp, quiet);
             if (quiet) {  // the transform this tail tested at and did not store
@@ -4853,11 +4667,9 @@ __device__ __forceinline__ int fold_update_pair(const PairArgs& a, const WorkArg
 // statement's "memory" clobber keeps the compiler from moving the store past the add.  An acq_rel add
 // would instead put an L2 write-back (buffer_wbl2) in every workgroup — 1.7-6.5 us each by the same
 // section's price list — for an ordering the sc1 accesses already give.
-#ifndef ICP4R_UPD_OCC
-#define ICP4R_UPD_OCC 4  // (experiment) workgroups per CU of fold_update_kernel: 4, 3 or 2
-#endif
+// (launch bound: 4 workgroups per CU; 3 and 2, held down with dynamic LDS, were the experiment)
 template <bool PEND>
-__global__ __launch_bounds__(kFoldWG, ICP4R_UPD_OCC) void fold_update_kernel(PairArgs a, WorkArgs w, int tail_test, int order_ncu,
+__global__ __launch_bounds__(kFoldWG, 4) void fold_update_kernel(PairArgs a, WorkArgs w, int tail_test, int order_ncu,
                                                                              int silent) {
     __shared__ FoldShared sh;
     __shared__ OrderShared osh;
@@ -4917,12 +4729,6 @@ struct ResShared {
     SolveShared s;
 };
 
-#ifndef ICP4R_RES_LB
-#define ICP4R_RES_LB 4  // columns' loads in flight at a time
-#endif
-#ifndef ICP4R_RES_FOLD
-#define ICP4R_RES_FOLD fold_row  // pass A's fold (fold_row8 / fold_row3: fewer / more registers)
-#endif
 typedef float fcols __attribute__((ext_vector_type(kResCols)));  // one coordinate of a thread's columns
 typedef uint32_t ucols __attribute__((ext_vector_type(kResCols)));
 __device__ __forceinline__ int uni(int j) { return __builtin_amdgcn_readfirstlane(j); }
@@ -4936,92 +4742,6 @@ __device__ __forceinline__ _Float16 half_down(float x) {
         h = __builtin_bit_cast(_Float16, b);
     }
     return h;
-}
-
-// fold_row with three register sets of 16 in rotation (two groups' loads in flight while one is summed)
-__device__ __forceinline__ float fold_row3(const float* f, int len, float acc) {
-    int k = 0;
-    if (len >= 48) {
-        float4 a[4], b[4], c[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) a[u] = *reinterpret_cast<const float4*>(f + 4 * u);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) b[u] = *reinterpret_cast<const float4*>(f + 16 + 4 * u);
-        for (; k + 48 <= len; k += 48) {
-            // the loads past this round re-read group 0 harmlessly when nothing follows
-            const int n1 = (k + 64 <= len) ? k + 48 : 0, n2 = (k + 80 <= len) ? k + 64 : 0;
-#pragma unroll
-            for (int u = 0; u < 4; ++u) c[u] = *reinterpret_cast<const float4*>(f + k + 32 + 4 * u);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) acc = chain_add4(acc, a[u]);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) a[u] = *reinterpret_cast<const float4*>(f + n1 + 4 * u);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) acc = chain_add4(acc, b[u]);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) b[u] = *reinterpret_cast<const float4*>(f + n2 + 4 * u);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) acc = chain_add4(acc, c[u]);
-        }
-        // a, b hold [k, k + 16) and [k + 16, k + 32) when they exist
-        if (k + 16 <= len) {
-#pragma unroll
-            for (int u = 0; u < 4; ++u) acc = chain_add4(acc, a[u]);
-            k += 16;
-            if (k + 16 <= len) {
-#pragma unroll
-                for (int u = 0; u < 4; ++u) acc = chain_add4(acc, b[u]);
-                k += 16;
-            }
-        }
-    }
-    return k < len ? fold_row(f + k, len - k, acc) : acc;
-}
-
-// A chain's step over an LDS row (16-B aligned) with three register sets of 8 in rotation (two groups'
-// loads in flight while one is summed): 24 registers — the on-chip update's fold lane shares its wave's
-// allocation with the held points
-__device__ __forceinline__ float fold_row8(const float* f, int len, float acc) {
-    int k = 0;
-    if (len >= 24) {
-        float4 a[2], b[2], c[2];
-#pragma unroll
-        for (int u = 0; u < 2; ++u) a[u] = *reinterpret_cast<const float4*>(f + 4 * u);
-#pragma unroll
-        for (int u = 0; u < 2; ++u) b[u] = *reinterpret_cast<const float4*>(f + 8 + 4 * u);
-        for (; k + 24 <= len; k += 24) {
-            const int n1 = (k + 32 <= len) ? k + 24 : 0, n2 = (k + 40 <= len) ? k + 32 : 0;
-#pragma unroll
-            for (int u = 0; u < 2; ++u) c[u] = *reinterpret_cast<const float4*>(f + k + 16 + 4 * u);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int u = 0; u < 2; ++u) acc = chain_add4(acc, a[u]);
-#pragma unroll
-            for (int u = 0; u < 2; ++u) a[u] = *reinterpret_cast<const float4*>(f + n1 + 4 * u);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int u = 0; u < 2; ++u) acc = chain_add4(acc, b[u]);
-#pragma unroll
-            for (int u = 0; u < 2; ++u) b[u] = *reinterpret_cast<const float4*>(f + n2 + 4 * u);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int u = 0; u < 2; ++u) acc = chain_add4(acc, c[u]);
-        }
-        if (k + 8 <= len) {  // a holds [k, k + 8)
-#pragma unroll
-            for (int u = 0; u < 2; ++u) acc = chain_add4(acc, a[u]);
-            k += 8;
-            if (k + 8 <= len) {
-#pragma unroll
-                for (int u = 0; u < 2; ++u) acc = chain_add4(acc, b[u]);
-                k += 8;
-            }
-        }
-    }
-    return k < len ? fold_tail<float>(f + k, len - k, acc) : acc;
 }
 
 __device__ __forceinline__ int res_update_pair(const PairArgs& a, const WorkArgs& w, int tail_test, int p,
@@ -5058,7 +4778,7 @@ __device__ __forceinline__ int res_update_pair(const PairArgs& a, const WorkArgs
     // access), so every loop over them is a loop, not 32 unrolled copies — an unrolled kernel's code
     // (~0.5 MB) had been fetched from L2 instruction by instruction
     fcols px, py, pz, qx, qy;
-    constexpr int kLB = ICP4R_RES_LB;
+    constexpr int kLB = 4;  // columns' loads in flight at a time
     float4 lv_[kLB], lt_[kLB];  // a batch in flight
     auto issue = [&](int b) __attribute__((always_inline)) {
 #pragma unroll
@@ -5120,7 +4840,7 @@ __device__ __forceinline__ int res_update_pair(const PairArgs& a, const WorkArgs
         __syncthreads();  // column K staged; buffer (K + 1) & 1 folded (column K - 1)
         if (wave == 0 && lane < 7) {
             fold_prio(true);
-            acc = ICP4R_RES_FOLD(buf + ((K & 1) * 7 + lane) * kResRowA, min(kResWG, n - K * kResWG), acc);
+            acc = fold_row(buf + ((K & 1) * 7 + lane) * kResRowA, min(kResWG, n - K * kResWG), acc);
             fold_prio(false);
         }
         RES_TICKX(K);
@@ -5367,8 +5087,8 @@ __device__ __forceinline__ int res_update_pair(const PairArgs& a, const WorkArgs
         const float d2 = l2_simple(ox, oy, oz, qx[j], qy[j], sh.qz[i]);
         const bool hit = valid & cache_hit(Lm.x, d2);
         if (valid) {
-            st_v4<1>(&X[i], make_float4(ox, oy, oz, Lm.x));
-            st_sc<1>(&uu[i], Lm.y);
+            X[i] = make_float4(ox, oy, oz, Lm.x);
+            uu[i] = Lm.y;
         }
         const bool miss = valid && !hit;
         const int k = wave_append(miss, &sh.mcount);
@@ -5493,24 +5213,6 @@ __global__ __launch_bounds__(kWideWG) void fold_update_wide_kernel(PairArgs a, W
     if (ticks) w.ticks[1] = __builtin_amdgcn_s_memrealtime();
     fold_pass_b<kWideWG, kWideChunkP, kWideRow, true>(kp, fin, sh.buf, sh.s);
     if (ticks) w.ticks[2] = __builtin_amdgcn_s_memrealtime();
-#ifdef ICP4R_SOLVE_PROBE
-    // debug: the rotation of this sigma twice, back to back (ticks[5], [6]: durations) — a cold
-    // instruction cache shows as a first run much slower than the second
-    if (ticks) {
-        for (int rep = 0; rep < 2; ++rep) {
-            const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
-            float z;
-            asm volatile("v_mov_b32 %0, 0" : "=v"(z));
-            float sg[9], R[9];
-#pragma unroll
-            for (int k = 0; k < 9; ++k) sg[k] = sh.s.sigmaf[k] + z;
-            umeyama_rotation_f32_reg(sg, R);
-#pragma unroll
-            for (int k = 0; k < 9; ++k) asm volatile("" ::"v"(R[k]));
-            w.ticks[5 + rep] = __builtin_amdgcn_s_memrealtime() - t0;
-        }
-    }
-#endif
     if (tid == 0) solve_pair<kNumericsPCL>(sh.s, st, kp);
     __syncthreads();
     if (ticks) w.ticks[3] = __builtin_amdgcn_s_memrealtime();
@@ -5542,15 +5244,10 @@ constexpr int kHeldFill0 = 128;                       // first filler thread
 template <bool S0>
 constexpr int held_fillers() { return S0 ? 11 * 64 : kWideWG - kHeldFill0; }  // 704 / 896
 static_assert(2 * held_fillers<false>() <= kWideChunkP, "pass A's chunk fits the wide buffers");
-#ifndef ICP4R_PACKED_FILL
-#define ICP4R_PACKED_FILL 0  // (experiment) the held pass B's products with packed float math
-#endif
 // pass B's first chunk in the small form (steps; 0: every chunk T steps).  Measured (two A/B rounds):
 // C1 0.384 (0) / 0.381 (128) / 0.385 (64) / 0.388 ms (32); at 8k any ramp lost (C2 1.162 -> 1.175
 // with 128, 1.197 with 32), so the 8k form keeps uniform chunks.
-#ifndef ICP4R_PASSB_RAMP
-#define ICP4R_PASSB_RAMP 128
-#endif
+constexpr int kHeldPassBRamp = 128;
 static_assert(kHeldMaxN == 10 * held_fillers<false>() && kHeldSmallN == 3 * held_fillers<true>(), "held sizes");
 
 // PCL's sequential double chain over LDS, few registers (the MSE fallback beside the held records)
@@ -5575,7 +5272,7 @@ __device__ __forceinline__ double fold_seq_d_lite(const double* f, int len, doub
 template <int HOLD, bool S0>
 __global__ __launch_bounds__(kWideWG) void fold_update_held_kernel(PairArgs a, WorkArgs w) {
     constexpr int kHeldFillers = held_fillers<S0>();
-    constexpr int kPassBRamp = S0 ? ICP4R_PASSB_RAMP : 0;
+    constexpr int kPassBRamp = S0 ? kHeldPassBRamp : 0;
     constexpr int kHeldCH = 2 * kHeldFillers;  // pass A chunk: two slots of every filler
     __shared__ WideShared sh;
     const int p = xcd_remap(blockIdx.x, gridDim.x);
@@ -5853,23 +5550,6 @@ __global__ __launch_bounds__(kWideWG) void fold_update_held_kernel(PairArgs a, W
                 for (int k = 0; k < HOLD; ++k) {
                     if ((pk[k] & 15) != c + 1) continue;
                     const int off = pk[k] >> 4;
-#if ICP4R_PACKED_FILL
-                    // packed (v_pk_add / v_pk_mul: two IEEE float operations per instruction, the same
-                    // roundings — contraction is off): the fill is VALU work of 14 waves on 4 SIMDs
-                    typedef float f2 __attribute__((ext_vector_type(2)));
-                    const f2 s01 = f2{sx[k], sy[k]} - f2{ms[0], ms[1]};
-                    const f2 d01 = f2{dx[k], dy[k]} - f2{md[0], md[1]};
-                    const float s2 = sz[k] - ms[2], d2 = dz[k] - md[2];
-                    const float dvs[3] = {d01.x, d01.y, d2};
-                    float* o = b + off;
-#pragma unroll
-                    for (int ra = 0; ra < 3; ++ra) {
-                        const f2 pr = f2{dvs[ra], dvs[ra]} * s01;
-                        o[(ra * 3 + 0) * stride] = pr.x;
-                        o[(ra * 3 + 1) * stride] = pr.y;
-                        o[(ra * 3 + 2) * stride] = dvs[ra] * s2;
-                    }
-#else
                     const float sv[3] = {sx[k] - ms[0], sy[k] - ms[1], sz[k] - ms[2]};
                     const float dv[3] = {dx[k] - md[0], dy[k] - md[1], dz[k] - md[2]};
                     float* o = b + off;
@@ -5877,7 +5557,6 @@ __global__ __launch_bounds__(kWideWG) void fold_update_held_kernel(PairArgs a, W
                     for (int ra = 0; ra < 3; ++ra)
 #pragma unroll
                         for (int rb = 0; rb < 3; ++rb) o[(ra * 3 + rb) * stride] = dv[ra] * sv[rb];
-#endif
                 }
             };
             fill(0);
@@ -6189,15 +5868,11 @@ __global__ __launch_bounds__(kFinWG) void finish_kernel(PairArgs a, WorkArgs w) 
 constexpr int kSoloWG = kLdsWG;
 constexpr int kSoloFitChunk = 960;  // fitness chunk: 15 waves fill, wave 0 lane 0 folds
 constexpr int kSoloGrp = 4;         // the first pass' sorted positions in flight per thread
-// LDS.  (compile-time) ICP4R_SOLO_RESIDENT=1: the pair's target tile stays resident for the whole registration,
+// LDS: the pair's target tile stays resident for the whole registration,
 // and the search's per-wave state, the update's fold buffers (192-point chunks), the test's bitmap
-// and records and the fitness chunks take turns in the 18 KB beside it.  0: the tile and the
-// update's 512-point fold buffers (fold_update_kernel's) take turns in one region, the tile
-// restaged from the L2 for each search.
-#ifndef ICP4R_SOLO_RESIDENT
-#define ICP4R_SOLO_RESIDENT 1
-#endif
-constexpr bool kSoloResident = ICP4R_SOLO_RESIDENT != 0;
+// and records and the fitness chunks take turns in the 18 KB beside it.  (The other layout — the tile and
+// 512-point fold buffers taking turns in one region, the tile restaged from the L2 for each search —
+// was the experiment.)
 struct SoloTile {
     v4f tl[kLdsTargets];
     alignas(16) float bx[kLdsTargets / kLdsLeaf][6];
@@ -6208,7 +5883,7 @@ struct SoloSearch {  // the search's per-wave state
     uint32_t sec[kLdsWaves][64];
     uint16_t items[kLdsWaves][kRing + 64];
 };
-constexpr int kSoloChunk = kSoloResident ? 192 : kFoldChunkP;  // fold chunk (points)
+constexpr int kSoloChunk = 192;  // fold chunk (points)
 constexpr int kSoloRow = kSoloChunk + kFoldPad;
 struct SoloFold {  // the update
     alignas(16) float buf[2][9][kSoloRow];
@@ -6217,14 +5892,13 @@ struct SoloFold {  // the update
     SolveShared sv;
 };
 // the test's LDS miss records (24 B each), after the bitmap and its prefixes, in the region they share
-constexpr int kSoloRecs = ((int)(kSoloResident ? sizeof(SoloSearch) : sizeof(SoloTile)) - 8 * kNeedWords) / 24 & ~15;
+constexpr int kSoloRecs = ((int)sizeof(SoloSearch) - 8 * kNeedWords) / 24 & ~15;
 struct SoloTest {  // the cached-neighbour test: the miss bitmap, its word prefixes, the miss records
     uint32_t need[kNeedWords];
     int32_t pre[kNeedWords];
     float4 lv[kSoloRecs];
     uint2 lm[kSoloRecs];
 };
-#if ICP4R_SOLO_RESIDENT
 struct SoloShared {
     SoloTile t;
     union {
@@ -6236,23 +5910,6 @@ struct SoloShared {
     int32_t wtot[kLdsWaves];  // per-wave counts (the test's misses, the fitness count)
     int32_t mcount;           // the test's LDS record count
 };
-#define SOLO_T(sh) (sh).t
-#define SOLO_S(sh) (sh).u.s
-#else
-struct SoloShared {
-    union {
-        SoloTile t;
-        SoloFold f;
-        SoloTest c;
-        alignas(16) double fit[2][kSoloFitChunk];
-    } u;
-    SoloSearch s;
-    int32_t wtot[kLdsWaves];
-    int32_t mcount;
-};
-#define SOLO_T(sh) (sh).u.t
-#define SOLO_S(sh) (sh).s
-#endif
 #define SOLO_F(sh) (sh).u.f
 #define SOLO_C(sh) (sh).u.c
 #define SOLO_FIT(sh) (sh).u.fit
@@ -6359,21 +6016,14 @@ __global__ __launch_bounds__(kSoloWG) void solo_kernel(PairArgs a, WorkArgs w, i
     const int64_t xs0 = (int64_t)p * w.x_stride;
     const bool valid = uload(&st.phase) != kPhaseInvalid;
     const int nsb = (((m + kLdsLeaf - 1) / kLdsLeaf) + kSuper - 1) / kSuper;
-    const LdsTile tile{SOLO_T(sh).tl, SOLO_T(sh).bx, SOLO_T(sh).sbx};
+    const LdsTile tile{sh.t.tl, sh.t.bx, sh.t.sbx};
     RunStats rs;
     auto search = [&](int nlist, bool keys) {
         __syncthreads();  // the list (global, this workgroup's) and the region's previous use
-        v4f isl, ish;
-        if (kSoloResident) {
-            const v4f* sbg = reinterpret_cast<const v4f*>(w.sbox + (int64_t)p * 2 * w.sb_stride);
-            const int sbl = min(lane, nsb - 1);
-            isl = sbg[2 * sbl];
-            ish = sbg[2 * sbl + 1];
-        } else {
-            stage_tile<kSoloWG>(tile, w, p, nsb, isl, ish);
-            __syncthreads();
-        }
-        lds_runs<true>(tile, SOLO_S(sh).best[wave], SOLO_S(sh).sec[wave], SOLO_S(sh).items[wave], w.qv + xs0, w.qm + xs0, nlist, m, nsb,
+        const v4f* sbg = reinterpret_cast<const v4f*>(w.sbox + (int64_t)p * 2 * w.sb_stride);
+        const int sbl = min(lane, nsb - 1);
+        v4f isl = sbg[2 * sbl], ish = sbg[2 * sbl + 1];
+        lds_runs<true>(tile, sh.u.s.best[wave], sh.u.s.sec[wave], sh.u.s.items[wave], w.qv + xs0, w.qm + xs0, nlist, m, nsb,
                        isl, ish, a, w, p, xs0, w.X + xs0, w.nn_key + xs0, keys, false, rs);
         __syncthreads();
     };
@@ -6389,10 +6039,8 @@ __global__ __launch_bounds__(kSoloWG) void solo_kernel(PairArgs a, WorkArgs w, i
         tk_last = now;
     };
     if (valid) {
-        if (kSoloResident) {
-            v4f isl, ish;
-            stage_tile<kSoloWG>(tile, w, p, nsb, isl, ish);  // (the search reloads its boxes)
-        }
+        v4f isl, ish;
+        stage_tile<kSoloWG>(tile, w, p, nsb, isl, ish);  // (the search reloads its boxes)
         float T[16];
 #pragma unroll
         for (int q = 0; q < 16; ++q) T[q] = 0.0f;
@@ -6573,7 +6221,7 @@ hipError_t launch_index(const PairArgs& a, const WorkArgs& w, int npairs, hipStr
         return hipGetLastError();
     }
     hipLaunchKernelGGL(index_kernel, dim3(npairs, tgt_only ? 1 : 2), dim3(kIdxWG), 0, st, a, w);
-    if (w.src_by_tgt && w.kdn && !(ICP4R_FUSE_SRC_ORDER && tgt_only))
+    if (w.src_by_tgt && w.kdn && !tgt_only)
         hipLaunchKernelGGL(src_order_kernel, dim3(npairs), dim3(kSoWG), 0, st, a, w);
     if ((w.kd_index & 1) && w.t_stride > kKdMaxN && (w.leaf == 16 || w.leaf == 32))
         hipLaunchKernelGGL(index_refine_kernel, dim3(nch, npairs), dim3(kIdxWG), 0, st, a, w);
@@ -6700,13 +6348,10 @@ hipError_t launch_update(const PairArgs& a, const WorkArgs& w, int npairs, int m
                  !w.sums_tail && (!tail_test || (w.sq && w.sm && w.need && w.miss_cnt)))
             hipLaunchKernelGGL(fold_update_res_kernel, dim3(npairs), dim3(kResWG), 0, st, a, w, tail_test, order_ncu);
         else if (w.lazy_x && pending)
-            hipLaunchKernelGGL(fold_update_kernel<true>, dim3(npairs), dim3(kFoldWG),
-                               ICP4R_UPD_OCC >= 4 ? 0 : (ICP4R_UPD_OCC == 3 ? 12000 : 20000), st, a, w, tail_test,
-                               order_ncu, 0);
+            hipLaunchKernelGGL(fold_update_kernel<true>, dim3(npairs), dim3(kFoldWG), 0, st, a, w, tail_test, order_ncu, 0);
         else
-            hipLaunchKernelGGL(fold_update_kernel<false>, dim3(npairs), dim3(kFoldWG),
-                               ICP4R_UPD_OCC >= 4 ? 0 : (ICP4R_UPD_OCC == 3 ? 12000 : 20000), st, a, w, tail_test,
-                               order_ncu, (w.lazy_x && tail_test && silent) ? 1 : 0);
+            hipLaunchKernelGGL(fold_update_kernel<false>, dim3(npairs), dim3(kFoldWG), 0, st, a, w, tail_test, order_ncu,
+                               (w.lazy_x && tail_test && silent) ? 1 : 0);
     } else {
         hipLaunchKernelGGL(update_f64_kernel, dim3(npairs), dim3(kUpdWG), 0, st, a, w);
     }

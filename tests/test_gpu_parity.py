@@ -509,7 +509,8 @@ def test_stage_sel_identical(gpu_ctx, oracle_mod, plan):
     """Small ranked work items stage only the superblocks their queries can reach (plan option
     stage_sel: items of at most that many misses): off, tiny, the default and every item give
     bit-identical registrations and fitness, equal to the oracle — a superblock the search needed and
-    the mask left out would be read as the previous item's targets."""
+    the mask left out would be read as copies of target 0 (tile_load fills unselected superblocks
+    with it), not as the previous item's targets."""
     import icp4r
 
     pairs = [_pair(2900 + k, 8192 if k % 5 == 0 else 4096) for k in range(300)]

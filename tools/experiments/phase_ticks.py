@@ -38,8 +38,6 @@ def ticks(ctx) -> list[float]:
                                  "to_fill": (t[12] - t[30]) * 0.01, "fold0": (t[27] - t[13]) * 0.01,
                                  "wait1": (t[28] - t[27]) * 0.01 if t[28] else None,
                                  "fold1": (t[29] - t[28]) * 0.01 if t[29] else None}
-    if t[5] and t[6] and t[5] < 100000:  # ICP4R_SOLVE_PROBE builds: the rotation twice, back to back
-        out["rotation_x2"] = [t[5] * 0.01, t[6] * 0.01]
     return out
 
 

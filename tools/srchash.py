@@ -2,8 +2,11 @@
 
 profiles/pmc_traffic.json is stamped with the sha256 of the profiled library AND with this hash: the
 library hash changes with any source of the .so (GICP, the map, ego velocity), this one only with
-the ICP kernels, their host-side launch code, the headers they include and the build flags — a PMC
-row stays valid for a library rebuilt after a change elsewhere (bench.py names which hash matched).
+the ICP kernels (csrc/icp4r_kernels.hip), their host-side launch code, the headers they include and the
+Makefile's text — a PMC row stays valid for a library rebuilt after a change elsewhere (bench.py names
+which hash matched).  Flags given on make's command line (EXTRA=-D...) are not part of the Makefile's
+text, so the hash cannot tell such a variant from the default build; the kernel sources keep one
+compile-time switch, the diagnostic ICP4R_WG_TICKS.
 """
 from __future__ import annotations
 
