@@ -1,5 +1,5 @@
 // icp4r_device.hpp — device-side helpers shared by the kernel translation units
-// (icp4r_kernels.hip, icp4r_gicp.hip): scalar-cache pointers, the XCD-aware work mapping, the
+// (icp4r_index.hip, icp4r_kernels.hip, icp4r_gicp.hip): scalar-cache pointers, the XCD-aware work mapping, the
 // slotted work counters and the NN key.
 #pragma once
 

@@ -207,6 +207,44 @@ constexpr int kMaxTickPasses = 64;  // passes with their own slots (later passes
 // first per-pass slot of a batch of npairs (after the pair-0 stamps and the per-pair debug slots)
 inline int64_t pass_tick_base(int npairs) { return 32 + 20 * (int64_t)npairs; }
 
+// ---- the ICP path (launch_index, launch_index_cloud: icp4r_index.hip; the others: icp4r_kernels.hip).
+// One registration = SURVEY.md §3.2 / Appendix A.  It runs on the
+// device as a fixed sequence of launches with no host synchronisation: per-pair phase flags (PairState)
+// let a finished pair's workgroups return at once.  run_pairs (icp4r_capi.cpp) picks one of:
+//
+//   batched (many pairs, targets <= kLdsMaxTargets; up to kMaxGroups pair groups, a stream each)
+//     launch_init, launch_index                       validate, X := guess * src; kd / Morton orders, boxes
+//     per iteration:
+//       launch_nn_lds      [nn_cache_test_kernel] [nn_order_kernel] nn_lds_kernel — the test and the work
+//                          list only where the previous update's fused tail did not make them
+//       launch_update      fold_update_kernel (or its res form): correspondences -> fold passes A and B ->
+//                          3x3 solve -> hasConverged -> the tail: X := T_inc * X, the next pass' test and list
+//     launch_fitness_prep, launch_nn_lds(fitness), launch_finish
+//
+//   pruned / tile (single pairs, small batches, targets of any size; one stream)
+//     launch_init, launch_index
+//     per iteration:
+//       launch_nn_tile     [nn_seed_kernel] nn_tile_kernel [corr_kernel] — one tile: the search alone
+//         or launch_nn_pruned   [nn_seed_kernel] nn_pruned_kernel<Q, B> [corr_kernel]   (plan option nn_tile = 0)
+//       launch_update      fold_update_held_kernel / fold_update_wide_kernel (at most one pair per CU), else
+//                          fold_update_kernel; F64 numerics: update_f64_kernel
+//     [launch_fitness_prep], the search once more (fitness), launch_finish
+//     brute force (small targets, ICP4R_NN_BRUTE): launch_nn in the search's place, launch_update with
+//     need_corr (corr_kernel first), no launch_index
+//
+//   solo (the tile plan's pairs when every target fits one LDS tile; sources <= kSoloMaxN by default)
+//     launch_init, launch_index, launch_solo          solo_kernel: every iteration, the fitness pass and the
+//                                                     result row of a pair by one workgroup in one launch
+//
+// nn_kernel and nn_pruned_kernel hold Q queries per lane in VGPRs and stream targets through the scalar
+// cache: the target address is wave-uniform, so each target point lands in SGPRs and is broadcast to 64
+// lanes x Q queries with no LDS traffic; the batched, tiled and solo searches stage a target tile in LDS
+// and evaluate (query, block) work items instead.  Per (query, target) the VALU executes 3 sub + 3 mul +
+// 2 add (FLANN's L2_Simple, unfused) and a compare/select.  Every NN result is a u64 key (d² bits, target
+// index) whose minimum is PCL's answer (lowest index among ties), so pruning, visiting order and target
+// splits cannot change it.  Determinism: fixed-order
+// reductions only (xor-butterfly per wave, waves in index order, the PCL-numerics folds sequential in
+// source order); no float atomics.
 hipError_t launch_init(const PairArgs& a, const WorkArgs& w, int npairs, hipStream_t st);
 hipError_t launch_nn(int q, bool packed, const PairArgs& a, const WorkArgs& w, int npairs, int max_n,
                      int fitness_pass, hipStream_t st);

@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Per-kernel register / scratch / LDS table from hipcc's -Rpass-analysis=kernel-resource-usage remarks.
 
-  tools/resource_usage.py [kernel.hip] [-I dir ...]     (default: icp-4dradar_amd/csrc/icp4r_kernels.hip)
+  tools/resource_usage.py [kernel.hip] [-I dir ...]     (default: every ICP unit of the Makefile's ICP_UNITS)
 
-Compiles the file for gfx950 with the library's flags (nothing is written) and prints one line per
+Compiles each file for gfx950 with the library's flags (nothing is written) and prints one line per
 kernel: VGPRs, SGPRs, scratch bytes per lane, LDS bytes per block.  Used to check that a refactor
 leaves a kernel's register allocation unchanged (diff two runs).
 """
@@ -11,6 +11,8 @@ import os
 import re
 import subprocess
 import sys
+
+from srchash import icp_units
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -35,18 +37,24 @@ def usage(path, incs):
     return rows
 
 
-def main():
-    args = sys.argv[1:]
-    path = args[0] if args and not args[0].startswith("-I") else os.path.join(ROOT, "icp-4dradar_amd/csrc/icp4r_kernels.hip")
-    incs = [a[2:] for a in args if a.startswith("-I")] or [os.path.dirname(path)]
-    demangle = subprocess.run(["c++filt"], input="\n".join(r["name"] for r in usage(path, incs)), capture_output=True,
-                              text=True)
+def report(path, incs):
     rows = usage(path, incs)
+    demangle = subprocess.run(["c++filt"], input="\n".join(r["name"] for r in rows), capture_output=True, text=True)
     names = demangle.stdout.splitlines() if demangle.returncode == 0 else [r["name"] for r in rows]
     for r, n in zip(rows, names):
         n = re.sub(r"\(.*\)$", "", n)
         print(f"{n:60s} VGPR {r.get('VGPRs', '?'):>4} SGPR {r.get('TotalSGPRs', '?'):>4} "
               f"scratch {r.get('ScratchSize [bytes/lane]', '?'):>4} LDS {r.get('LDS Size [bytes/block]', '?'):>6}")
+
+
+def main():
+    args = sys.argv[1:]
+    if args and not args[0].startswith("-I"):
+        paths = [args[0]]
+    else:
+        paths = [os.path.join(ROOT, "icp-4dradar_amd/csrc", u + ".hip") for u in icp_units()]
+    for path in paths:
+        report(path, [a[2:] for a in args if a.startswith("-I")] or [os.path.dirname(path)])
 
 
 if __name__ == "__main__":
