@@ -9,6 +9,12 @@ features within 4 float ulp (the device rounds the double atan2 / asin; glibc's 
 node calls, are off by an ulp in ~16 % / ~4 % of cases); with identical features, every
 hypothesis score and the winner identical, A and b within 1e-12, the static mask identical and Vxyz
 within 1e-9 (both sum the normal equations in double, in different orders).
+
+tests/test_ego_edges.py holds the branches these scans do not reach, under the same bars: explicit
+`iterations` at the hypothesis- and point-tile edges, scans below 5 points, a winner that is the first
+of many tied maxima, the batch entry point against the oracle (empty, tiny and oversized scans,
+guard bytes, a caller's stream) and feature edge records; for small or ill-conditioned scans its
+Vxyz bar is derived from cond(KtK).  The map tests' edge-filter bar is in tests/test_map_exact.py.
 """
 import numpy as np
 import pytest
