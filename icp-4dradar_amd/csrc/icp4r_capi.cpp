@@ -866,7 +866,10 @@ int icp4r_align(icp4r_ctx* ctx, const float* src, int32_t n, int32_t src_stride_
         HIP_TRY(hipMemcpyAsync(ha.data(), ctx->aligned.p, ha.size() * sizeof(float), hipMemcpyDeviceToHost, st));
     }
     HIP_TRY(hipStreamSynchronize(st));
-    if (aligned_out && n > 0) {
+    // (an invalid pair — empty target, non-finite input — computes nothing: Registration::align returns
+    // before it touches the output, and the device buffer still holds an earlier call's cloud)
+    const bool computed = out->status != ICP4R_E_EMPTY && out->status != ICP4R_E_NONFINITE;
+    if (aligned_out && n > 0 && computed) {
         unsigned char* o = reinterpret_cast<unsigned char*>(aligned_out);
         for (int32_t i = 0; i < n; ++i) {
             float* q = reinterpret_cast<float*>(o + (size_t)i * out_stride_bytes);

@@ -3421,7 +3421,8 @@ __device__ __forceinline__ int fold_update_pair(const PairArgs& a, const WorkArg
     if (tail) {
         // (the Σs-folding tail loads its first group itself: a second prefetch layout held across the
         // solve spilled to scratch)
-        if (!sums_tail) tail_prefetch<kFoldWG, kTailPer>(w, p, n, tf);
+        // (n = 0: no group to load — its first group would start a whole group before the pair's slots)
+        if (!sums_tail && n > 0) tail_prefetch<kFoldWG, kTailPer>(w, p, n, tf);
         for (int k = tid; k < ((n + 31) >> 5); k += kFoldWG) need[k] = 0u;
         if (tid == 0) sh.mcount = 0;
     }
@@ -4282,7 +4283,9 @@ __global__ __launch_bounds__(kWideWG) void fold_update_held_kernel(PairArgs a, W
                 }
             }
         };
-        load(0, 2);
+        // (an empty source holds nothing: the clamped index n - 1 would be -1, in front of the pair's
+        // slots, and in key mode no key of the pair has been written for the gather to follow)
+        if (n > 0) load(0, 2);
         store_a(0, true);
         for (int c = 0; c < nch; ++c) {
             __syncthreads();

@@ -492,7 +492,8 @@ class IterativeClosestPoint:
         r, aligned = ctx.align(self._src, self._tgt, self._p, guess=guess, want_aligned=True)
         self._result = r
         out = self._src.copy()
-        out[:, :3] = aligned[:, :3]
+        if r.status not in (E_EMPTY, E_NONFINITE):  # (else nothing was computed: the output is the input)
+            out[:, :3] = aligned[:, :3]
         if output is not None:
             output[...] = out
             return output

@@ -146,7 +146,8 @@ int icp4r_destroy(icp4r_ctx* ctx);
  * stride in bytes (PCL PointXYZI: 32, float4: 16, the .bin record: 20); x, y, z are the first
  * three floats of a point, intensity the fourth when stride >= 16.  guess: 16 floats
  * column-major or NULL.  aligned_out (optional): n points written with out_stride_bytes,
- * x, y, z = transformCloud(input, final), intensity copied when out_stride_bytes >= 16. */
+ * x, y, z = transformCloud(input, final), intensity copied when out_stride_bytes >= 16; left
+ * untouched when nothing was computed (ICP4R_E_EMPTY, ICP4R_E_NONFINITE). */
 int icp4r_align(icp4r_ctx* ctx, const float* src, int32_t n, int32_t src_stride_bytes, const float* tgt,
                 int32_t m, int32_t tgt_stride_bytes, const float* guess, const icp4r_params* params,
                 icp4r_result* out, float* aligned_out, int32_t out_stride_bytes);

@@ -205,6 +205,8 @@ class IterativeClosestPoint {
         converged_ = result_.converged != 0;
         for (int k = 0; k < 16; ++k) final_.data()[k] = result_.T[k];
         output = *src_;  // output := input, then xyz := final * input (intensity kept)
+        // (nothing computed: icp4r_align wrote no aligned cloud; final is the identity, output the input)
+        if (rc == ICP4R_E_EMPTY || rc == ICP4R_E_NONFINITE) return;
         for (int32_t i = 0; i < n; ++i) {
             output.points[i].x = aligned[4 * (size_t)i + 0];
             output.points[i].y = aligned[4 * (size_t)i + 1];
