@@ -83,7 +83,10 @@ int check_params(const icp4r_gicp_params* p) {
 // grids measured slower even for a single 8k scan: the map call 1.27 -> 1.36 ms with its source by
 // brute force, an 8k pair at k = 20 0.96 -> 2.07 ms — every candidate ran the insertion chain in
 // some lane of the wave.)
-bool cov_brute(int opt_val, const icp4r_pipe::Plan& pl) { return !pl.pruned || opt_val == 1; }
+// Also with plan option leaf = 32: the k-NN walk (gicp_knn_cov_kernel) reads an index of 16-target
+// blocks only, and the two kernels find the same neighbour sets, so the option changes no result. Every
+// caller decides this before it queues anything (run_gicp: before its aux-stream fork).
+bool cov_brute(int opt_val, const icp4r_pipe::Plan& pl) { return !pl.pruned || pl.leaf != 16 || opt_val == 1; }
 
 // k-NN covariances of the clouds (cloud, off, cnt) of npairs pairs: brute force, or pruned over an
 // index of each cloud (index_kernel with the cloud as its target; w's index buffers must fit max_n

@@ -275,6 +275,9 @@ __global__ __launch_bounds__(kCovWG) void gicp_knn_cov_kernel(const float4* __re
     const int chunks = gridDim.x;
     const int g = xcd_remap(blockIdx.x + chunks * blockIdx.y, chunks * gridDim.y);
     const int p = g / chunks, ch = g - p * chunks;
+    // a pair init_kernel found invalid has no index (index_cloud skips it): its part of tsort holds an
+    // earlier call's, whose point indices — the rows written below — may lie past this pair's rows
+    if (w.state[p].phase == kPhaseInvalid) return;
     const int n = uload(cnt + p);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int base = ch * (kCovWG / L) + wave * Q;

@@ -372,7 +372,8 @@ struct GicpArgs {
 hipError_t launch_gicp_init(const float* guess, GicpState* gs, int npairs, hipStream_t st);
 hipError_t launch_gicp_cov(const float4* cloud, const int64_t* off, const int32_t* cnt, int npairs, int max_n,
                            int64_t stride, int k, int reg, double* cov, int lanes, hipStream_t st);
-// k-NN covariances over a Morton index of the cloud itself (w.tsort / tbox / sbox, leaf 16)
+// k-NN covariances over a Morton index of the cloud itself (w.tsort / tbox / sbox, leaf 16; pairs whose
+// w.state is invalid have no index and are skipped)
 hipError_t launch_gicp_knn_cov(const float4* cloud, const int64_t* off, const int32_t* cnt, const WorkArgs& w,
                                int npairs, int max_n, int64_t stride, int k, int reg, double* cov, int lanes,
                                hipStream_t st);

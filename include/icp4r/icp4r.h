@@ -234,7 +234,9 @@ int icp4r_nn_stats(icp4r_ctx* ctx, icp4r_nn_stats_t* out);
 
 /* Plan options (A/B experiments and diagnostics): how a registration is laid out on the device —
  * which search and update kernels run, grid shapes, pair groups on streams, debug stamps.  No option
- * changes a result (the parity tests assert bit-identical registrations across them), and an option
+ * changes a result (the parity tests assert bit-identical registrations across them; where a kernel
+ * has no form for an option's value the call takes an equivalent one, e.g. the generalized ICP's
+ * brute-force covariances at "leaf" = 32, it does not fail), and an option
  * never set keeps its measured-best default (DESIGN.md §6 lists every name and default).  Options
  * belong to a context and apply to its later calls; the library reads no environment variable.
  * An unknown name, or a value outside the option's range (e.g. "groups" above 3: a fourth pair

@@ -23,6 +23,12 @@
  *
  * Parity status: UNPINNED by the reference (fast_gicp is absent; the node needs ROS).  Pinned by
  * the C restatement oracle/gicp_oracle.c and known-answer tests (tests/test_gicp.py).
+ *
+ * Plan options (icp4r_set_plan_option) change no result here either (tests/test_gicp_plans.py).  With
+ * "leaf" = 32 the covariances come from the brute-force kernel: the k-NN walk reads an index of
+ * 16-target blocks only.  An empty source, like a pair whose distance gate rejects every
+ * correspondence, is ICP4R_OK: converged after 0 iterations at the guess with 0 correspondences
+ * (its fitness DBL_MAX); an empty target is ICP4R_E_EMPTY.
  */
 #ifndef ICP4R_GICP_H
 #define ICP4R_GICP_H
