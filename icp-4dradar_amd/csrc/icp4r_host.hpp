@@ -86,6 +86,14 @@ namespace icp4r_host {
 void comm_detach(icp4r_comm* c);
 }  // namespace icp4r_host
 
+struct icp4r_map;
+namespace icp4r_host {
+// icp4r_destroy, with the context's device current and its stream idle and still alive: frees the
+// map's device memory and events and leaves it detached (ctx = nullptr, empty) — every entry on it
+// then fails with ICP4R_E_INVALID and icp4r_map_destroy only deletes the host struct
+void map_detach(icp4r_map* m);
+}  // namespace icp4r_host
+
 struct icp4r_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -104,6 +112,9 @@ struct icp4r_ctx {
     uint64_t plan_set = 0;
     // RCCL communicators created on this context (icp4r_multi.cpp): detached by icp4r_destroy
     std::vector<icp4r_comm*> comms;
+    // map stores created on this context (icp4r_map.cpp): registered by icp4r_map_create, removed by
+    // icp4r_map_destroy, detached by icp4r_destroy — a map may outlive its context
+    std::vector<icp4r_map*> maps;
     // HIP events on the launch stream: the dominant NN kernel (the batched search, or the whole NN
     // launch of the other plans), the cache-test kernel, the update kernel, whole registrations
     std::vector<icp4r_host::EventPair> nn_events, test_events, upd_events, batch_events;

@@ -304,8 +304,30 @@ struct Mat3x4d {
 };
 hipError_t launch_associate(const float4* in, int64_t n, const Mat3x4d& M, float4* out, hipStream_t st);
 int64_t sector_blocks(int64_t n);
+// The searches and the delete are one stable compaction (count per block, scan, ordered write) with
+// the keep test as a parameter; counts / offsets hold sector_blocks(n) entries, out every kept point.
 hipError_t launch_sector(const float4* map, int64_t n, const SectorArgs& a, int32_t* counts, int32_t* offsets,
                          int32_t* total, float4* out, hipStream_t st);
+struct BoxArgs {
+    float lo[3], hi[3];  // min <= p && max > p
+};
+hipError_t launch_box(const float4* map, int64_t n, const BoxArgs& b, int32_t* counts, int32_t* offsets,
+                      int32_t* total, float4* out, hipStream_t st);
+hipError_t launch_radius(const float4* map, int64_t n, const float* c, float radius, int32_t* counts,
+                         int32_t* offsets, int32_t* total, float4* out, hipStream_t st);
+// keeps the points in none of the nb boxes (device, nb x 6)
+hipError_t launch_outside_boxes(const float4* map, int64_t n, const float* d_boxes, int32_t nb, int32_t* counts,
+                                int32_t* offsets, int32_t* total, float4* out, hipStream_t st);
+// Downsampled insert of na arrivals into n0 stored points (n0 + na < 2^31): the new store to out (room
+// for n0 + na points), its size to *total, the reference's counter to **counter (in the scratch).
+// scratch: ds_layout(n0, na).bytes; counts / offsets: sector_blocks(n0 + na) entries.
+struct DsLayout {
+    size_t smin, rep, scount, swin, pairs_a, pairs_b, sslot, akeep, rcounts, roffsets, counter, bytes;
+};
+DsLayout ds_layout(int64_t n0, int64_t na);
+hipError_t launch_downsample(const float4* map, int64_t n0, const float4* arr, int64_t na, float ds, void* scratch,
+                             int32_t* counts, int32_t* offsets, int32_t* total, float4* out, int32_t** counter,
+                             hipStream_t st);
 
 // ---- radar ego velocity (icp4r_ego.hip)
 struct EgoArgs {

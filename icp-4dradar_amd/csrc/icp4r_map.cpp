@@ -1,13 +1,21 @@
 // icp4r_map.cpp — C ABI of the scan-to-map store (include/icp4r/icp4r_map.h).
 //
-// Host-side mirror of the reference's ikd-Tree as radar_odometry.cpp uses it (:92, :347-348,
-// :382-396): an append-only float4 store in HBM that grows by doubling, and Sector_Search as a
-// device stream compaction (icp4r_map.hip).  No CPU fallback: every entry fails with
-// ICP4R_E_HIP if the device path cannot run.
+// Host-side mirror of the reference's ikd-Tree (radar_odometry.cpp:92, :347-348, :382-396, and the
+// map-maintenance calls of ikd_Tree.h:238-245): a dense float4 store in HBM, in insertion order, that
+// grows by doubling.  Sector_Search, Box_Search, Radius_Search and Delete_Point_Boxes are one device
+// stream compaction with the keep test as a parameter, the downsampling Add_Points a per-cell
+// reduction plus one compaction (icp4r_map.hip); the two edits compact into a second buffer of the
+// store's capacity and swap.  No CPU fallback: every entry fails with ICP4R_E_HIP if the device path
+// cannot run.
+//
+// Lifetime: a context keeps a list of its maps.  icp4r_destroy frees the device side of each and
+// detaches it (ctx = nullptr); a detached map answers every entry with ICP4R_E_INVALID without
+// touching HIP, and icp4r_map_destroy only deletes the host struct.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <string.h>
 
+#include <algorithm>
 #include <vector>
 
 #include "icp4r/icp4r_map.h"
@@ -21,15 +29,36 @@ using icp4r_host::fail;
 using icp4r_host::pack_host;
 
 struct icp4r_map {
-    icp4r_ctx* ctx = nullptr;
-    float4* pts = nullptr;  // [cap] insertion order
+    icp4r_ctx* ctx = nullptr;  // nullptr: detached (the context was destroyed)
+    float4* pts = nullptr;     // [cap] insertion order
+    float4* alt = nullptr;     // [cap] the edits' second buffer (allocated at the first edit), or nullptr
     int64_t n = 0, cap = 0;
-    DevBuf staging, counts, offsets, total, out;
+    DevBuf staging, counts, offsets, total, out, boxes, ds;
     std::vector<EventPair> events;
     size_t used = 0;
 };
 
 namespace {
+
+#define MAP_LIVE(m)                                                                        \
+    do {                                                                                   \
+        if (!(m)->ctx) return fail(ICP4R_E_INVALID, "the map's context was destroyed");    \
+    } while (0)
+
+// Frees everything the map holds on the device (the context's device is current).
+void release_device(icp4r_map* m) {
+    if (m->pts) (void)hipFree(m->pts);
+    if (m->alt) (void)hipFree(m->alt);
+    m->pts = m->alt = nullptr;
+    for (DevBuf* b : {&m->staging, &m->counts, &m->offsets, &m->total, &m->out, &m->boxes, &m->ds}) b->release();
+    for (auto& e : m->events) {
+        (void)hipEventDestroy(e.start);
+        (void)hipEventDestroy(e.stop);
+    }
+    m->events.clear();
+    m->used = 0;
+    m->n = m->cap = 0;
+}
 
 // Grow the store to hold `need` points, keeping the first map->n (doubling: amortised O(1) append).
 int grow(icp4r_map* m, int64_t need) {
@@ -49,6 +78,19 @@ int grow(icp4r_map* m, int64_t need) {
     if (m->pts) HIP_TRY(hipFree(m->pts));
     m->pts = p;
     m->cap = cap;
+    if (m->alt) {  // the second buffer follows the capacity: allocated again at the next edit
+        float4* a = m->alt;
+        m->alt = nullptr;
+        HIP_TRY(hipFree(a));
+    }
+    return ICP4R_OK;
+}
+
+// The edits' second buffer, of the store's capacity (at least one allocation's worth).
+int ensure_alt(icp4r_map* m) {
+    int rc;
+    if (m->cap == 0 && (rc = grow(m, 1))) return rc;
+    if (!m->alt) HIP_TRY(hipMalloc(&m->alt, (size_t)m->cap * sizeof(float4)));
     return ICP4R_OK;
 }
 
@@ -60,19 +102,16 @@ int stage(icp4r_map* m, const float* pts, int64_t n, int32_t stride, std::vector
     return ICP4R_OK;
 }
 
-int sector_launch(icp4r_map* m, const float* center, float radius, float heading, float4* out, int32_t* count,
-                  hipStream_t st) {
-    if (!center) return fail(ICP4R_E_INVALID, "center is NULL");
-    if (!(radius >= 0.0f)) return fail(ICP4R_E_INVALID, "radius must be >= 0");
-    const int64_t nblk = icp4r::sector_blocks(m->n);
+int ensure_blocks(icp4r_map* m, int64_t n) {
+    const int64_t nblk = icp4r::sector_blocks(n);
     HIP_TRY(m->counts.ensure((size_t)(nblk > 0 ? nblk : 1) * sizeof(int32_t)));
     HIP_TRY(m->offsets.ensure((size_t)(nblk > 0 ? nblk : 1) * sizeof(int32_t)));
-    icp4r::SectorArgs a;
-    a.cx = center[0];
-    a.cy = center[1];
-    a.cz = center[2];
-    a.radius = radius;
-    a.heading = heading;
+    return ICP4R_OK;
+}
+
+// Runs `launch` (stream -> hipError_t) between a pair of the map's timing events.
+template <class Launch>
+int timed(icp4r_map* m, hipStream_t st, Launch launch) {
     if (m->used == m->events.size()) {
         EventPair e;
         HIP_TRY(hipEventCreate(&e.start));
@@ -81,13 +120,118 @@ int sector_launch(icp4r_map* m, const float* center, float radius, float heading
     }
     EventPair& ev = m->events[m->used++];
     HIP_TRY(hipEventRecord(ev.start, st));
-    HIP_TRY(icp4r::launch_sector(m->pts, m->n, a, static_cast<int32_t*>(m->counts.p),
-                                 static_cast<int32_t*>(m->offsets.p), count, out, st));
+    HIP_TRY(launch(st));
     HIP_TRY(hipEventRecord(ev.stop, st));
     return ICP4R_OK;
 }
 
+// The three filters, by their arguments: each launches the compaction of the store into out / count.
+struct SectorQuery {
+    const float* center;
+    float radius, heading;
+};
+struct BoxQuery {
+    const float* box6;
+};
+struct RadiusQuery {
+    const float* center;
+    float radius;
+};
+
+int check_query(const SectorQuery& q) {
+    if (!q.center) return fail(ICP4R_E_INVALID, "center is NULL");
+    if (!(q.radius >= 0.0f)) return fail(ICP4R_E_INVALID, "radius must be >= 0");
+    return ICP4R_OK;
+}
+int check_query(const BoxQuery& q) { return q.box6 ? ICP4R_OK : fail(ICP4R_E_INVALID, "box is NULL"); }
+int check_query(const RadiusQuery& q) {
+    if (!q.center) return fail(ICP4R_E_INVALID, "center is NULL");
+    if (!(q.radius >= 0.0f)) return fail(ICP4R_E_INVALID, "radius must be >= 0");
+    return ICP4R_OK;
+}
+
+hipError_t launch_query(icp4r_map* m, const SectorQuery& q, float4* out, int32_t* count, hipStream_t st) {
+    icp4r::SectorArgs a;
+    a.cx = q.center[0];
+    a.cy = q.center[1];
+    a.cz = q.center[2];
+    a.radius = q.radius;
+    a.heading = q.heading;
+    return icp4r::launch_sector(m->pts, m->n, a, static_cast<int32_t*>(m->counts.p), static_cast<int32_t*>(m->offsets.p),
+                                count, out, st);
+}
+hipError_t launch_query(icp4r_map* m, const BoxQuery& q, float4* out, int32_t* count, hipStream_t st) {
+    icp4r::BoxArgs b;
+    memcpy(b.lo, q.box6, sizeof(b.lo));
+    memcpy(b.hi, q.box6 + 3, sizeof(b.hi));
+    return icp4r::launch_box(m->pts, m->n, b, static_cast<int32_t*>(m->counts.p), static_cast<int32_t*>(m->offsets.p),
+                             count, out, st);
+}
+hipError_t launch_query(icp4r_map* m, const RadiusQuery& q, float4* out, int32_t* count, hipStream_t st) {
+    return icp4r::launch_radius(m->pts, m->n, q.center, q.radius, static_cast<int32_t*>(m->counts.p),
+                                static_cast<int32_t*>(m->offsets.p), count, out, st);
+}
+
+template <class Query>
+int query_launch(icp4r_map* m, const Query& q, float4* out, int32_t* count, hipStream_t st) {
+    int rc;
+    if ((rc = check_query(q))) return rc;
+    if ((rc = ensure_blocks(m, m->n))) return rc;
+    return timed(m, st, [&](hipStream_t s) { return launch_query(m, q, out, count, s); });
+}
+
+// The host variants: the kept points to host memory; *out_n is set even when they do not fit.
+template <class Query>
+int query_host(icp4r_map* m, const Query& q, float* out, int64_t out_cap, int64_t* out_n, const char* what) {
+    if (!m || !out_n || (out_cap > 0 && !out)) return fail(ICP4R_E_INVALID, "NULL argument");
+    MAP_LIVE(m);
+    HIP_TRY(hipSetDevice(m->ctx->device));
+    hipStream_t st = m->ctx->stream;
+    HIP_TRY(m->out.ensure((size_t)(m->n > 0 ? m->n : 1) * sizeof(float4)));
+    HIP_TRY(m->total.ensure(sizeof(int32_t)));
+    int rc;
+    if ((rc = query_launch(m, q, static_cast<float4*>(m->out.p), static_cast<int32_t*>(m->total.p), st))) return rc;
+    int32_t cnt = 0;
+    HIP_TRY(hipMemcpyAsync(&cnt, m->total.p, sizeof(cnt), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *out_n = cnt;
+    if (cnt > out_cap) return fail(ICP4R_E_TOO_LARGE, "%s kept %d points, out_cap %lld", what, cnt, (long long)out_cap);
+    if (cnt > 0) {
+        HIP_TRY(hipMemcpyAsync(out, m->out.p, (size_t)cnt * sizeof(float4), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    return ICP4R_OK;
+}
+
+template <class Query>
+int query_device(icp4r_map* m, const Query& q, float* d_out, int32_t* d_count, void* hip_stream) {
+    if (!m || !d_out || !d_count) return fail(ICP4R_E_INVALID, "NULL argument");
+    MAP_LIVE(m);
+    HIP_TRY(hipSetDevice(m->ctx->device));
+    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : m->ctx->stream;
+    return query_launch(m, q, reinterpret_cast<float4*>(d_out), d_count, st);
+}
+
+// After an edit compacted the new store into m->alt and its size into m->total: adopt it.
+int adopt_alt(icp4r_map* m, int64_t* new_n) {
+    int32_t cnt = 0;
+    HIP_TRY(hipMemcpyAsync(&cnt, m->total.p, sizeof(cnt), hipMemcpyDeviceToHost, m->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(m->ctx->stream));
+    std::swap(m->pts, m->alt);
+    *new_n = cnt;
+    return ICP4R_OK;
+}
+
 }  // namespace
+
+namespace icp4r_host {
+
+void map_detach(icp4r_map* m) {
+    release_device(m);
+    m->ctx = nullptr;
+}
+
+}  // namespace icp4r_host
 
 extern "C" {
 
@@ -97,19 +241,19 @@ int icp4r_map_create(icp4r_ctx* ctx, icp4r_map** out) {
     if (ctx->device < 0) return fail(ICP4R_E_INVALID, "icp4r_map_create: a context without a device");
     icp4r_map* m = new icp4r_map();
     m->ctx = ctx;
+    ctx->maps.push_back(m);
     *out = m;
     return ICP4R_OK;
 }
 
 int icp4r_map_destroy(icp4r_map* m) {
     if (!m) return ICP4R_OK;
-    (void)hipSetDevice(m->ctx->device);
-    (void)hipStreamSynchronize(m->ctx->stream);
-    if (m->pts) (void)hipFree(m->pts);
-    for (DevBuf* b : {&m->staging, &m->counts, &m->offsets, &m->total, &m->out}) b->release();
-    for (auto& e : m->events) {
-        (void)hipEventDestroy(e.start);
-        (void)hipEventDestroy(e.stop);
+    if (m->ctx) {
+        auto& maps = m->ctx->maps;
+        maps.erase(std::remove(maps.begin(), maps.end(), m), maps.end());
+        (void)hipSetDevice(m->ctx->device);
+        (void)hipStreamSynchronize(m->ctx->stream);
+        release_device(m);
     }
     delete m;
     return ICP4R_OK;
@@ -117,8 +261,9 @@ int icp4r_map_destroy(icp4r_map* m) {
 
 int icp4r_map_add_points(icp4r_map* m, const float* pts, int64_t n, int32_t stride_bytes, int32_t downsample_on) {
     if (!m) return fail(ICP4R_E_INVALID, "map is NULL");
+    MAP_LIVE(m);
     if (downsample_on)
-        return fail(ICP4R_E_INVALID, "Add_Points with downsample_on is not on this path (radar_odometry.cpp:390 passes false)");
+        return fail(ICP4R_E_INVALID, "Add_Points with downsample_on carries no box length: use icp4r_map_add_points_downsample");
     int rc;
     if ((rc = check_cloud(pts, n, stride_bytes, "points"))) return rc;
     if (n == 0) return ICP4R_OK;
@@ -132,8 +277,69 @@ int icp4r_map_add_points(icp4r_map* m, const float* pts, int64_t n, int32_t stri
     return ICP4R_OK;
 }
 
+int icp4r_map_add_points_downsample(icp4r_map* m, const float* pts, int64_t n, int32_t stride_bytes, float box_length,
+                                    int64_t* counter) {
+    if (!m || !counter) return fail(ICP4R_E_INVALID, "map/counter is NULL");
+    MAP_LIVE(m);
+    if (!(box_length > 0.0f) || !isfinite(box_length)) return fail(ICP4R_E_INVALID, "box_length must be finite and > 0");
+    int rc;
+    if ((rc = check_cloud(pts, n, stride_bytes, "points"))) return rc;
+    *counter = 0;
+    if (n == 0) return ICP4R_OK;
+    if (m->n + n >= ((int64_t)1 << 30)) return fail(ICP4R_E_TOO_LARGE, "downsampled insert: %lld points", (long long)(m->n + n));
+    HIP_TRY(hipSetDevice(m->ctx->device));
+    hipStream_t st = m->ctx->stream;
+    if ((rc = grow(m, m->n + n))) return rc;  // the new store holds at most every stored and every arriving point
+    if ((rc = ensure_alt(m))) return rc;
+    std::vector<float> h;
+    if ((rc = stage(m, pts, n, stride_bytes, h))) return rc;
+    HIP_TRY(m->ds.ensure(icp4r::ds_layout(m->n, n).bytes));
+    HIP_TRY(m->total.ensure(sizeof(int32_t)));
+    if ((rc = ensure_blocks(m, m->n + n))) return rc;
+    int32_t* d_counter = nullptr;
+    if ((rc = timed(m, st, [&](hipStream_t s) {
+            return icp4r::launch_downsample(m->pts, m->n, static_cast<const float4*>(m->staging.p), n, box_length, m->ds.p,
+                                            static_cast<int32_t*>(m->counts.p), static_cast<int32_t*>(m->offsets.p),
+                                            static_cast<int32_t*>(m->total.p), m->alt, &d_counter, s);
+        })))
+        return rc;
+    int32_t cnt = 0;
+    HIP_TRY(hipMemcpyAsync(&cnt, d_counter, sizeof(cnt), hipMemcpyDeviceToHost, st));
+    if ((rc = adopt_alt(m, &m->n))) return rc;  // synchronises: h and cnt are done with
+    *counter = cnt;
+    return ICP4R_OK;
+}
+
+int icp4r_map_delete_boxes(icp4r_map* m, const float* boxes, int32_t nb, int64_t* deleted) {
+    if (!m || !deleted || (nb > 0 && !boxes)) return fail(ICP4R_E_INVALID, "NULL argument");
+    MAP_LIVE(m);
+    if (nb < 0) return fail(ICP4R_E_INVALID, "nb must be >= 0");
+    *deleted = 0;
+    if (nb == 0 || m->n == 0) return ICP4R_OK;
+    HIP_TRY(hipSetDevice(m->ctx->device));
+    hipStream_t st = m->ctx->stream;
+    int rc;
+    if ((rc = ensure_alt(m))) return rc;
+    HIP_TRY(m->boxes.ensure((size_t)nb * 6 * sizeof(float)));
+    HIP_TRY(m->total.ensure(sizeof(int32_t)));
+    if ((rc = ensure_blocks(m, m->n))) return rc;
+    HIP_TRY(hipMemcpyAsync(m->boxes.p, boxes, (size_t)nb * 6 * sizeof(float), hipMemcpyHostToDevice, st));
+    if ((rc = timed(m, st, [&](hipStream_t s) {
+            return icp4r::launch_outside_boxes(m->pts, m->n, static_cast<const float*>(m->boxes.p), nb,
+                                               static_cast<int32_t*>(m->counts.p), static_cast<int32_t*>(m->offsets.p),
+                                               static_cast<int32_t*>(m->total.p), m->alt, s);
+        })))
+        return rc;
+    int64_t kept = 0;
+    if ((rc = adopt_alt(m, &kept))) return rc;
+    *deleted = m->n - kept;
+    m->n = kept;
+    return ICP4R_OK;
+}
+
 int icp4r_map_build(icp4r_map* m, const float* pts, int64_t n, int32_t stride_bytes) {
     if (!m) return fail(ICP4R_E_INVALID, "map is NULL");
+    MAP_LIVE(m);
     int rc;
     if ((rc = check_cloud(pts, n, stride_bytes, "points"))) return rc;
     m->n = 0;  // KD_TREE::Build replaces the tree
@@ -143,6 +349,7 @@ int icp4r_map_build(icp4r_map* m, const float* pts, int64_t n, int32_t stride_by
 int icp4r_map_add_scan(icp4r_map* m, const float* scan, int64_t n, int32_t stride_bytes, const double* R,
                        const double* t, float* world_out) {
     if (!m || !R || !t) return fail(ICP4R_E_INVALID, "map/R/t is NULL");
+    MAP_LIVE(m);
     int rc;
     if ((rc = check_cloud(scan, n, stride_bytes, "scan"))) return rc;
     if (n == 0) return ICP4R_OK;
@@ -163,43 +370,42 @@ int icp4r_map_add_scan(icp4r_map* m, const float* scan, int64_t n, int32_t strid
 
 int icp4r_map_size(const icp4r_map* m, int64_t* n) {
     if (!m || !n) return fail(ICP4R_E_INVALID, "NULL argument");
+    MAP_LIVE(m);
     *n = m->n;
     return ICP4R_OK;
 }
 
 int icp4r_map_sector_search(icp4r_map* m, const float* center, float radius, float heading_deg, float* out,
                             int64_t out_cap, int64_t* out_n) {
-    if (!m || !out_n || (out_cap > 0 && !out)) return fail(ICP4R_E_INVALID, "NULL argument");
-    HIP_TRY(hipSetDevice(m->ctx->device));
-    hipStream_t st = m->ctx->stream;
-    HIP_TRY(m->out.ensure((size_t)(m->n > 0 ? m->n : 1) * sizeof(float4)));
-    HIP_TRY(m->total.ensure(sizeof(int32_t)));
-    int rc;
-    if ((rc = sector_launch(m, center, radius, heading_deg, static_cast<float4*>(m->out.p),
-                            static_cast<int32_t*>(m->total.p), st)))
-        return rc;
-    int32_t cnt = 0;
-    HIP_TRY(hipMemcpyAsync(&cnt, m->total.p, sizeof(cnt), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    *out_n = cnt;
-    if (cnt > out_cap) return fail(ICP4R_E_TOO_LARGE, "sector search kept %d points, out_cap %lld", cnt, (long long)out_cap);
-    if (cnt > 0) {
-        HIP_TRY(hipMemcpyAsync(out, m->out.p, (size_t)cnt * sizeof(float4), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    return ICP4R_OK;
+    return query_host(m, SectorQuery{center, radius, heading_deg}, out, out_cap, out_n, "sector search");
 }
 
 int icp4r_map_sector_search_device(icp4r_map* m, const float* center, float radius, float heading_deg, float* d_out,
                                    int32_t* d_count, void* hip_stream) {
-    if (!m || !d_out || !d_count) return fail(ICP4R_E_INVALID, "NULL argument");
-    HIP_TRY(hipSetDevice(m->ctx->device));
-    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : m->ctx->stream;
-    return sector_launch(m, center, radius, heading_deg, reinterpret_cast<float4*>(d_out), d_count, st);
+    return query_device(m, SectorQuery{center, radius, heading_deg}, d_out, d_count, hip_stream);
+}
+
+int icp4r_map_box_search(icp4r_map* m, const float* box6, float* out, int64_t out_cap, int64_t* out_n) {
+    return query_host(m, BoxQuery{box6}, out, out_cap, out_n, "box search");
+}
+
+int icp4r_map_box_search_device(icp4r_map* m, const float* box6, float* d_out, int32_t* d_count, void* hip_stream) {
+    return query_device(m, BoxQuery{box6}, d_out, d_count, hip_stream);
+}
+
+int icp4r_map_radius_search(icp4r_map* m, const float* center, float radius, float* out, int64_t out_cap,
+                            int64_t* out_n) {
+    return query_host(m, RadiusQuery{center, radius}, out, out_cap, out_n, "radius search");
+}
+
+int icp4r_map_radius_search_device(icp4r_map* m, const float* center, float radius, float* d_out, int32_t* d_count,
+                                   void* hip_stream) {
+    return query_device(m, RadiusQuery{center, radius}, d_out, d_count, hip_stream);
 }
 
 int icp4r_map_points_device(icp4r_map* m, const float** d_points, int64_t* n) {
     if (!m || !d_points || !n) return fail(ICP4R_E_INVALID, "NULL argument");
+    MAP_LIVE(m);
     *d_points = reinterpret_cast<const float*>(m->pts);
     *n = m->n;
     return ICP4R_OK;
@@ -207,6 +413,7 @@ int icp4r_map_points_device(icp4r_map* m, const float** d_points, int64_t* n) {
 
 int icp4r_map_time_ms(icp4r_map* m, double* avg_ms, int32_t* calls) {
     if (!m || !avg_ms) return fail(ICP4R_E_INVALID, "NULL argument");
+    MAP_LIVE(m);
     HIP_TRY(hipSetDevice(m->ctx->device));
     double tot = 0.0;
     for (size_t i = 0; i < m->used; ++i) {
@@ -222,6 +429,7 @@ int icp4r_map_time_ms(icp4r_map* m, double* avg_ms, int32_t* calls) {
 
 int icp4r_map_time_reset(icp4r_map* m) {
     if (!m) return fail(ICP4R_E_INVALID, "map is NULL");
+    MAP_LIVE(m);
     m->used = 0;
     return ICP4R_OK;
 }

@@ -75,6 +75,8 @@ MAP_EXPORTED_SYMBOLS = [
     "icp4r_map_create", "icp4r_map_destroy", "icp4r_map_build", "icp4r_map_add_points", "icp4r_map_add_scan",
     "icp4r_map_size", "icp4r_map_sector_search", "icp4r_map_sector_search_device", "icp4r_map_points_device",
     "icp4r_map_time_ms", "icp4r_map_time_reset",
+    "icp4r_map_add_points_downsample", "icp4r_map_delete_boxes", "icp4r_map_box_search", "icp4r_map_radius_search",
+    "icp4r_map_box_search_device", "icp4r_map_radius_search_device",
 ]
 
 
@@ -199,6 +201,12 @@ def load():
         "icp4r_map_points_device": (C.c_int, [vp, C.POINTER(vp), C.POINTER(i64)]),
         "icp4r_map_time_ms": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(i32)]),
         "icp4r_map_time_reset": (C.c_int, [vp]),
+        "icp4r_map_add_points_downsample": (C.c_int, [vp, vp, i64, i32, C.c_float, C.POINTER(i64)]),
+        "icp4r_map_delete_boxes": (C.c_int, [vp, vp, i32, C.POINTER(i64)]),
+        "icp4r_map_box_search": (C.c_int, [vp, vp, vp, i64, C.POINTER(i64)]),
+        "icp4r_map_radius_search": (C.c_int, [vp, vp, C.c_float, vp, i64, C.POINTER(i64)]),
+        "icp4r_map_box_search_device": (C.c_int, [vp, vp, vp, vp, vp]),
+        "icp4r_map_radius_search_device": (C.c_int, [vp, vp, C.c_float, vp, vp, vp]),
         # icp4r_multi.h
         "icp4r_shard": (C.c_int, [i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]),
         "icp4r_align_batch_multi": (C.c_int, [C.POINTER(vp), i32, vp, vp, vp, vp, vp, vp, i32, vp, C.POINTER(Params),

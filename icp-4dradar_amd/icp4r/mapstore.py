@@ -7,8 +7,12 @@ reference's radar_odometry node uses:
     pointAssociateToMap(...); ikd_Tree.Add_Points(.., false) :382-390
     ikd_Tree.Sector_Search(p_now, RADAR_RADIUS, heading, SubMap->points)   :396
 
+and ikd-Tree's map-maintenance calls (ikd_Tree.h:238-245): Delete_Point_Boxes, Box_Search,
+Radius_Search and the downsampling Add_Points(points, True).
+
 Same method names; clouds are (N, >=3) float32 arrays (x, y, z[, intensity]).  Device-resident and
-GPU-only: there is no CPU fallback (the library raises if it is missing).
+GPU-only: there is no CPU fallback (the library raises if it is missing).  A tree may outlive its
+context: once the context is closed every call on the tree raises and close() only frees the handle.
 """
 from __future__ import annotations
 
@@ -16,20 +20,25 @@ import ctypes as C
 
 import numpy as np
 
-from . import Context, _check, _cloud, _ptr, default_context, load
+from . import E_INVALID, Context, ICP4RError, _check, _cloud, _ptr, default_context, load
 
 RADAR_RADIUS = 80.0  # radar_odometry.cpp:36
 
 
 class KD_TREE:  # noqa: N801 — the reference's class name
-    """ikd-Tree replacement for radar_odometry's map: an append-only device store (nothing is ever
-    deleted on this path) with Sector_Search as a full filter in insertion order."""
+    """ikd-Tree replacement for radar_odometry's map: a dense device store in insertion order with
+    Sector_Search, Box_Search and Radius_Search as full filters, box deletion and the downsampling
+    insert (ikd-Tree's rebuild / rebalancing change no result and have no counterpart)."""
 
-    def __init__(self, delete_param: float = 0.5, balance_param: float = 0.6, box_length: float = 0.2,
+    def __init__(self, delete_param: float = 0.5, balance_param: float = 0.6, box_length: float | None = None,
                  ctx: Context | None = None):
         # delete/balance parameters steer ikd-Tree's rebalancing, which does not change query results;
-        # box_length is the downsample box, unused because the node adds with downsample_on = false.
-        self.delete_param, self.balance_param, self.downsample_size = delete_param, balance_param, box_length
+        # box_length is the downsample box of Add_Points(.., True) (the node adds with downsample_on = false).
+        # A tree that was never given a box (constructor or set_downsample_param) shows ikd-Tree's default
+        # of 0.2 but refuses Add_Points(.., True), as every tree did before the downsampling insert existed.
+        self.delete_param, self.balance_param = delete_param, balance_param
+        self.downsample_size = 0.2 if box_length is None else box_length
+        self._box_given = box_length is not None
         self._ctx = ctx or default_context()
         self._lib = load()
         self._h = C.c_void_p()
@@ -57,12 +66,46 @@ class KD_TREE:  # noqa: N801 — the reference's class name
 
     def set_downsample_param(self, box_length: float):
         self.downsample_size = box_length
+        self._box_given = True
 
     def Add_Points(self, points, downsample_on: bool = False) -> int:  # noqa: N802
+        """ikd-Tree's return value: the downsample counter, 0 without downsampling."""
         a, n, stride = _cloud(points)
-        _check(self._lib.icp4r_map_add_points(self._h, _ptr(a), n, stride, int(bool(downsample_on))),
-               "icp4r_map_add_points")
-        return 0  # ikd-Tree returns the downsample counter, 0 without downsampling
+        if downsample_on:
+            if not self._box_given:
+                raise ICP4RError(E_INVALID, "Add_Points(.., True): give the tree its downsample box first "
+                                            "(box_length or set_downsample_param)")
+            k = C.c_int64()
+            _check(self._lib.icp4r_map_add_points_downsample(self._h, _ptr(a), n, stride, float(self.downsample_size),
+                                                             C.byref(k)), "icp4r_map_add_points_downsample")
+            return k.value
+        _check(self._lib.icp4r_map_add_points(self._h, _ptr(a), n, stride, 0), "icp4r_map_add_points")
+        return 0
+
+    def Delete_Point_Boxes(self, boxes) -> int:  # noqa: N802
+        """Removes the points inside any box ((nb, 6): min xyz, max xyz; min <= p < max); -> how many."""
+        b = np.ascontiguousarray(np.asarray(boxes, np.float32).reshape(-1, 6))
+        k = C.c_int64()
+        _check(self._lib.icp4r_map_delete_boxes(self._h, _ptr(b) if len(b) else None, len(b), C.byref(k)),
+               "icp4r_map_delete_boxes")
+        return k.value
+
+    def _search(self, fn, name, *args) -> np.ndarray:
+        cap = self.size()
+        out = np.empty((max(cap, 1), 4), np.float32)
+        k = C.c_int64()
+        _check(fn(self._h, *args, _ptr(out), cap, C.byref(k)), name)
+        return out[:k.value].copy()
+
+    def Box_Search(self, box) -> np.ndarray:  # noqa: N802
+        """The stored points with min <= p < max, (K, 4) float32, insertion order.  box: 6 floats."""
+        b = np.ascontiguousarray(np.asarray(box, np.float32).reshape(6))
+        return self._search(self._lib.icp4r_map_box_search, "icp4r_map_box_search", _ptr(b))
+
+    def Radius_Search(self, point, radius: float) -> np.ndarray:  # noqa: N802
+        """The stored points with calc_dist(p, point) <= radius^2 (float), (K, 4) float32, insertion order."""
+        c = np.ascontiguousarray(np.asarray(point, np.float32).reshape(-1)[:3])
+        return self._search(self._lib.icp4r_map_radius_search, "icp4r_map_radius_search", _ptr(c), float(radius))
 
     def Sector_Search(self, point, radius: float, heading: float) -> np.ndarray:  # noqa: N802
         """The kept points, (K, 4) float32, insertion order (ikd-Tree: the same set, tree order)."""
@@ -98,6 +141,18 @@ class KD_TREE:  # noqa: N801 — the reference's class name
                                                         C.c_void_p(d_out), C.c_void_p(d_count),
                                                         C.c_void_p(stream) if stream else None),
                "icp4r_map_sector_search_device")
+
+    def box_search_device(self, box, d_out: int, d_count: int, stream=None):
+        b = np.ascontiguousarray(np.asarray(box, np.float32).reshape(6))
+        _check(self._lib.icp4r_map_box_search_device(self._h, _ptr(b), C.c_void_p(d_out), C.c_void_p(d_count),
+                                                     C.c_void_p(stream) if stream else None),
+               "icp4r_map_box_search_device")
+
+    def radius_search_device(self, point, radius: float, d_out: int, d_count: int, stream=None):
+        c = np.ascontiguousarray(np.asarray(point, np.float32).reshape(-1)[:3])
+        _check(self._lib.icp4r_map_radius_search_device(self._h, _ptr(c), float(radius), C.c_void_p(d_out),
+                                                        C.c_void_p(d_count), C.c_void_p(stream) if stream else None),
+               "icp4r_map_radius_search_device")
 
     def points_device(self) -> tuple[int, int]:
         p, n = C.c_void_p(), C.c_int64()

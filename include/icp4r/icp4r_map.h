@@ -15,16 +15,22 @@
  *   third_party/ikd-Tree/ikd_Tree.cpp:415-419 (Sector_Search), 422-497 (Add_Points),
  *   1098-1140 (Search_by_sector), 1427-1448 (calc_dist, calc_heading)
  *
- * On this path nothing is ever deleted and Sector_Search visits every node, so the store is an
- * append-only float4 (x, y, z, intensity) array in HBM and the query is a full filter at HBM
- * bandwidth, kept in insertion order (ikd-Tree returns the same SET in its tree's pre-order).  The
- * keep test is the reference's, C precedence included:
+ * Sector_Search visits every node, so the store is a dense float4 (x, y, z, intensity) array in HBM,
+ * in insertion order, and the query is a full filter at HBM bandwidth (ikd-Tree returns the same SET
+ * in its tree's pre-order).  The keep test is the reference's, C precedence included:
  *
  *   (d2 <= r*r && |h - heading| < 60) || |h - heading| > 300
  *
  * with d2 and h = calc_heading(p, center) (degrees, 0 along +y, +90 along -x) in the reference's
  * float/double mix.  Points with |dh| > 300 are kept whatever their distance (the reference's
  * operator-precedence quirk); a point AT the centre has h = NaN and is never kept.
+ *
+ * Map maintenance (ikd_Tree.h:238-245; the node itself does not call these): Delete_Point_Boxes,
+ * Box_Search, Radius_Search and the downsampling Add_Points(points, true).  Box membership is
+ * half-open in float, min[k] <= p[k] && max[k] > p[k]; radius membership is calc_dist(p, c) <=
+ * fl(r * r); a NaN coordinate or bound fails every comparison, so such a point is never found and
+ * never deleted.  Deleting leaves the survivors dense and in insertion order.  ikd-Tree's rebuild
+ * and rebalancing do not change any result and have no counterpart here.
  */
 #ifndef ICP4R_MAP_H
 #define ICP4R_MAP_H
@@ -38,17 +44,35 @@ extern "C" {
 typedef struct icp4r_map icp4r_map;
 
 /* A map store on the context's device (uses the context's stream; one map per context is
- * typical, several are allowed).  Destroy it before its context. */
+ * typical, several are allowed).  A map may outlive its context: icp4r_destroy frees the device memory
+ * of the context's maps and detaches them; every entry on a detached map then returns
+ * ICP4R_E_INVALID ("the map's context was destroyed") without touching the device, and
+ * icp4r_map_destroy only frees the host struct. */
 int icp4r_map_create(icp4r_ctx* ctx, icp4r_map** out);
 int icp4r_map_destroy(icp4r_map* map);
 
 /* KD_TREE::Build: replace the contents with n points (x, y, z[, intensity]) of stride_bytes. */
 int icp4r_map_build(icp4r_map* map, const float* pts, int64_t n, int32_t stride_bytes);
 
-/* KD_TREE::Add_Points(points, downsample_on): append.  downsample_on must be 0 — the node's only
- * call (radar_odometry.cpp:390); the voxel-downsampling insert is not part of this path
- * (ICP4R_E_INVALID). */
+/* KD_TREE::Add_Points(points, false): append.  downsample_on must be 0 — the node's only call
+ * (radar_odometry.cpp:390); this entry carries no box length, so a downsampling insert goes through
+ * icp4r_map_add_points_downsample (downsample_on != 0: ICP4R_E_INVALID). */
 int icp4r_map_add_points(icp4r_map* map, const float* pts, int64_t n, int32_t stride_bytes, int32_t downsample_on);
+
+/* KD_TREE::Add_Points(points, true) with downsample box box_length (finite, > 0; ikd_Tree.cpp:430-457).
+ * Of every downsample cell (floorf(p / box_length) per axis) that an arriving point falls in, only
+ * the point nearest to the cell's centre stays, among the cell's stored points and its arrivals: an
+ * arrival wins a tie against a stored point, the last tied arrival among arrivals, the lowest index
+ * among stored points.  Stored points of other cells, and stored points outside their own cell's
+ * float box, stay.  Surviving stored points keep their places; surviving arrivals follow in input
+ * order.  *counter = the reference's return value (the arrivals its sequential loop re-inserts). */
+int icp4r_map_add_points_downsample(icp4r_map* map, const float* pts, int64_t n, int32_t stride_bytes,
+                                    float box_length, int64_t* counter);
+
+/* KD_TREE::Delete_Point_Boxes: removes the points inside any of the nb boxes (nb x 6 floats: min xyz,
+ * max xyz); *deleted = how many (a point in several boxes counts once).  The survivors stay dense and
+ * in insertion order; the capacity never shrinks.  nb = 0 deletes nothing. */
+int icp4r_map_delete_boxes(icp4r_map* map, const float* boxes, int32_t nb, int64_t* deleted);
 
 /* pointAssociateToMap + Add_Points(.., false) for one scan: p_w = R * p + t in double (R row-major
  * 3x3 = Rtrans, t = t_w_curr; per row ((R0*x + R1*y) + R2*z) + t), stored as float, intensity
@@ -70,11 +94,22 @@ int icp4r_map_sector_search(icp4r_map* map, const float* center, float radius, f
 int icp4r_map_sector_search_device(icp4r_map* map, const float* center, float radius, float heading_deg,
                                    float* d_out, int32_t* d_count, void* hip_stream);
 
-/* The stored points (device, float4, insertion order) and their count. */
+/* KD_TREE::Box_Search / Radius_Search (radius >= 0): the stored points inside the box (6 floats) /
+ * within the radius of center, insertion order; arguments and overflow as icp4r_map_sector_search
+ * and icp4r_map_sector_search_device. */
+int icp4r_map_box_search(icp4r_map* map, const float* box6, float* out, int64_t out_cap, int64_t* out_n);
+int icp4r_map_radius_search(icp4r_map* map, const float* center, float radius, float* out, int64_t out_cap,
+                            int64_t* out_n);
+int icp4r_map_box_search_device(icp4r_map* map, const float* box6, float* d_out, int32_t* d_count, void* hip_stream);
+int icp4r_map_radius_search_device(icp4r_map* map, const float* center, float radius, float* d_out, int32_t* d_count,
+                                   void* hip_stream);
+
+/* The stored points (device, float4, insertion order) and their count; an edit (delete, downsampled
+ * insert, growth) moves them. */
 int icp4r_map_points_device(icp4r_map* map, const float** d_points, int64_t* n);
 
-/* Average device time (HIP events) of the sector-search launches since the last
- * icp4r_map_time_reset, and how many there were. */
+/* Average device time (HIP events) of the search, delete and downsampled-insert launches since the
+ * last icp4r_map_time_reset, and how many there were. */
 int icp4r_map_time_ms(icp4r_map* map, double* avg_ms, int32_t* calls);
 int icp4r_map_time_reset(icp4r_map* map);
 

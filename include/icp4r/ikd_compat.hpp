@@ -7,10 +7,13 @@
 //     #include <icp4r/ikd_compat.hpp>
 // and links libicp4r.so; `KD_TREE<pcl::PointXYZI> ikd_Tree(0.3, 0.6, 0.5);` and the Build /
 // set_downsample_param / Add_Points / Sector_Search calls stay textually unchanged.
+// ikd-Tree's map-maintenance calls carry the reference's signatures too (ikd_Tree.h:238-245):
+// Delete_Point_Boxes, Box_Search, Radius_Search, Add_Points(.., true) and BoxPointType.
 //
-// Semantics (include/icp4r/icp4r_map.h): an append-only device store — the node never deletes and
-// never adds with downsampling — and Sector_Search as a full filter with the reference's keep test,
-// returning the same set as ikd-Tree in insertion order.  Points are repacked to float4
+// Semantics (include/icp4r/icp4r_map.h): a dense device store in insertion order; Sector_Search,
+// Box_Search and Radius_Search are full filters with the reference's keep tests, returning the same
+// set as ikd-Tree in insertion order; deleting keeps the survivors' order; the downsampling insert
+// keeps, per touched downsample cell, the point nearest to the cell's centre.  Points are repacked to float4
 // (x, y, z, intensity) on the way in and restored on the way out, so PCL's 32-byte PointXYZI keeps
 // its intensity.  Each KD_TREE owns its own icp4r context (created on first use), so a
 // namespace-scope tree, as the node declares it, outlives nothing it depends on.
@@ -26,6 +29,11 @@
 
 namespace icp4r {
 
+struct BoxPointType {  // ikd-Tree's box: min <= p < max per axis
+    float vertex_min[3];
+    float vertex_max[3];
+};
+
 template <typename PointType>
 class KD_TREE {  // NOLINT — the reference's class name
   public:
@@ -37,7 +45,7 @@ class KD_TREE {  // NOLINT — the reference's class name
 #endif
 
     // delete / balance parameters steer ikd-Tree's rebalancing (no effect on query results);
-    // box_length is the downsample box, unused on the node's path (Add_Points(.., false)).
+    // box_length is the downsample box of Add_Points(.., true) (the node adds with false).
     explicit KD_TREE(float delete_param = 0.5f, float balance_param = 0.6f, float box_length = 0.2f)
         : delete_param_(delete_param), balance_param_(balance_param), downsample_size_(box_length) {}
     KD_TREE(const KD_TREE&) = delete;
@@ -58,28 +66,52 @@ class KD_TREE {  // NOLINT — the reference's class name
     template <typename Vec>
     int Add_Points(Vec& PointToAdd, bool downsample_on) {  // NOLINT
         std::vector<float> buf = pack(PointToAdd);
-        check(icp4r_map_add_points(map(), buf.data(), (int64_t)PointToAdd.size(), 16, downsample_on ? 1 : 0),
-              "Add_Points");
+        if (downsample_on) {
+            int64_t counter = 0;
+            check(icp4r_map_add_points_downsample(map(), buf.data(), (int64_t)PointToAdd.size(), 16, downsample_size_,
+                                                  &counter),
+                  "Add_Points");
+            return (int)counter;
+        }
+        check(icp4r_map_add_points(map(), buf.data(), (int64_t)PointToAdd.size(), 16, 0), "Add_Points");
         return 0;  // ikd-Tree returns its downsample counter: 0 without downsampling
+    }
+
+    int Delete_Point_Boxes(std::vector<BoxPointType>& BoxPoints) {  // NOLINT
+        static_assert(sizeof(BoxPointType) == 6 * sizeof(float), "BoxPointType is min xyz, max xyz");
+        int64_t deleted = 0;
+        check(icp4r_map_delete_boxes(map(), BoxPoints.empty() ? nullptr : BoxPoints[0].vertex_min,
+                                     (int32_t)BoxPoints.size(), &deleted),
+              "Delete_Point_Boxes");
+        return (int)deleted;
+    }
+
+    template <typename Vec>
+    void Box_Search(const BoxPointType& Box_of_Point, Vec& Storage) {  // NOLINT
+        float box[6];
+        for (int k = 0; k < 3; ++k) {
+            box[k] = Box_of_Point.vertex_min[k];
+            box[3 + k] = Box_of_Point.vertex_max[k];
+        }
+        search(Storage, "Box_Search", [&](float* out, int64_t cap, int64_t* k) {
+            return icp4r_map_box_search(map(), box, out, cap, k);
+        });
+    }
+
+    template <typename Vec>
+    void Radius_Search(PointType point, const float radius, Vec& Storage) {  // NOLINT
+        const float c[3] = {point.x, point.y, point.z};
+        search(Storage, "Radius_Search", [&](float* out, int64_t cap, int64_t* k) {
+            return icp4r_map_radius_search(map(), c, radius, out, cap, k);
+        });
     }
 
     template <typename Vec>
     void Sector_Search(PointType point, const float radius, const float heading, Vec& Storage) {  // NOLINT
-        Storage.clear();
-        int64_t cap = 0;
-        check(icp4r_map_size(map(), &cap), "Sector_Search");
-        std::vector<float> out((size_t)(cap > 0 ? cap : 1) * 4);
         const float c[3] = {point.x, point.y, point.z};
-        int64_t k = 0;
-        check(icp4r_map_sector_search(map(), c, radius, heading, out.data(), cap, &k), "Sector_Search");
-        Storage.resize((size_t)k);
-        for (int64_t i = 0; i < k; ++i) {
-            PointType& p = Storage[(size_t)i];
-            p.x = out[4 * i];
-            p.y = out[4 * i + 1];
-            p.z = out[4 * i + 2];
-            p.intensity = out[4 * i + 3];
-        }
+        search(Storage, "Sector_Search", [&](float* out, int64_t cap, int64_t* k) {
+            return icp4r_map_sector_search(map(), c, radius, heading, out, cap, k);
+        });
     }
 
     int size() {
@@ -97,6 +129,25 @@ class KD_TREE {  // NOLINT — the reference's class name
             check(icp4r_map_create(ctx_, &map_), "icp4r_map_create");
         }
         return map_;
+    }
+
+    // A host search into Storage: query(out, cap, &k) fills at most cap float4 rows; intensity restored.
+    template <typename Vec, typename Query>
+    void search(Vec& Storage, const char* what, Query query) {
+        Storage.clear();
+        int64_t cap = 0;
+        check(icp4r_map_size(map(), &cap), what);
+        std::vector<float> out((size_t)(cap > 0 ? cap : 1) * 4);
+        int64_t k = 0;
+        check(query(out.data(), cap, &k), what);
+        Storage.resize((size_t)k);
+        for (int64_t i = 0; i < k; ++i) {
+            PointType& p = Storage[(size_t)i];
+            p.x = out[4 * i];
+            p.y = out[4 * i + 1];
+            p.z = out[4 * i + 2];
+            p.intensity = out[4 * i + 3];
+        }
     }
 
     template <typename Vec>
@@ -123,5 +174,6 @@ class KD_TREE {  // NOLINT — the reference's class name
 }  // namespace icp4r
 
 #ifndef ICP4R_NO_IKD_ALIAS
+using icp4r::BoxPointType;
 using icp4r::KD_TREE;
 #endif

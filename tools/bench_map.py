@@ -9,6 +9,11 @@ radar_odometry loop body (radar_odometry.cpp:382-396) with the submap registered
   * loop body: add_scan + sector search into device memory + 20-iteration ICP of the next scan
     against the submap (count stays on the device as tgt_n).  Checked against the oracle.
 
+  * --edit: the map-maintenance calls on the same map instead — one Delete_Point_Boxes (a 20 m box
+    behind the vehicle), one Radius_Search (80 m) and one downsampled insert of a 6,554-point scan at
+    ds = 0.5, each timed with HIP events; bytes by the compaction formula.  --append PATH also appends
+    the JSON line to PATH (profiles/<run>/bench_map_edit.jsonl).
+
 One JSON line per measurement.
 """
 from __future__ import annotations
@@ -42,10 +47,67 @@ def pose(k: int):
     return R, t, deg
 
 
+def edit_leg(a, ctx, tree, center, heading):
+    """One Radius_Search, one Delete_Point_Boxes and one downsampled insert on the posed-scan map, each
+    timed by the store's HIP events (the launches only: uploads and read-backs are outside them)."""
+    import torch
+
+    n = tree.size()
+    dev = torch.device("cuda", 0)
+    d_out = torch.empty((n, 4), dtype=torch.float32, device=dev)
+    d_cnt = torch.zeros(1, dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()
+
+    def leg(name, points_in, kept, ms):
+        algo = 2 * 16 * points_in + 16 * kept  # 16 B per point read twice + 16 B per kept point
+        return {name + "_us": 1e3 * ms, name + "_points_in": points_in, name + "_kept": kept,
+                name + "_algorithmic_bytes": algo, name + "_TBps": algo / (ms * 1e-3) / 1e12}
+
+    out = {"measurement": "map_edit", "map_points": n, "first_measurement": True}
+    # the delete and the insert change the map, so each is timed once; a ten-point tree runs both first so
+    # that the timed calls do not include the kernels' first-launch load
+    warm = KD_TREE(0.3, 0.6, 0.5, ctx=ctx)
+    warm.Build(np.zeros((10, 4), np.float32))
+    warm.Delete_Point_Boxes([0.5, 0.5, 0.5, 1, 1, 1])
+    warm.Add_Points(np.ones((10, 4), np.float32), True)
+    warm.close()
+    tree.radius_search_device(center, RADAR_RADIUS, d_out.data_ptr(), d_cnt.data_ptr())  # warm-up
+    ctx.synchronize()
+    tree.reset_timers()
+    tree.radius_search_device(center, RADAR_RADIUS, d_out.data_ptr(), d_cnt.data_ptr())
+    ctx.synchronize()
+    out.update(leg("radius_search", n, int(d_cnt.item()), tree.time_ms()[0]))
+    # a 20 m box behind the vehicle: from 30 m to 10 m back along the heading (0 deg = +y, +90 = -x)
+    h = math.radians(heading)
+    back = center[:2] - 20.0 * np.array([-math.sin(h), math.cos(h)], np.float32)
+    box = np.array([back[0] - 10, back[1] - 10, -1e3, back[0] + 10, back[1] + 10, 1e3], np.float32)
+    tree.reset_timers()
+    deleted = tree.Delete_Point_Boxes(box)
+    out.update(leg("delete_boxes", n, n - deleted, tree.time_ms()[0]))
+    out["deleted"] = deleted
+    # the next scan, posed at the vehicle, through the downsampling insert
+    R, t, _ = pose(a.scans - 1)
+    scan = oracle.associate_to_map(synth.make_pair(9999, 6554).src_xyzi(), R, t)
+    n0 = tree.size()
+    tree.set_downsample_param(0.5)
+    tree.reset_timers()
+    counter = tree.Add_Points(scan, True)
+    out.update(leg("downsample_insert", n0 + len(scan), tree.size(), tree.time_ms()[0]))
+    out["downsample_counter"], out["downsample_ds"], out["scan_points"] = counter, 0.5, len(scan)
+    line = json.dumps(out)
+    print(line, flush=True)
+    if a.append:
+        os.makedirs(os.path.dirname(os.path.abspath(a.append)), exist_ok=True)
+        with open(a.append, "a") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scans", type=int, default=1500)
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--edit", action="store_true", help="time delete / radius search / downsampled insert instead")
+    ap.add_argument("--append", default=None, help="with --edit: also append the JSON line to this file")
     a = ap.parse_args()
     import torch
 
@@ -60,6 +122,11 @@ def main():
     n = tree.size()
     R, t, heading = pose(a.scans - 1)
     center = t.astype(np.float32)
+    if a.edit:
+        edit_leg(a, ctx, tree, center, heading)
+        tree.close()
+        ctx.close()
+        return
     dev = torch.device("cuda", 0)
     d_out = torch.empty((n + 8 * 6554, 4), dtype=torch.float32, device=dev)  # room for the loop's scans
     d_cnt = torch.zeros(1, dtype=torch.int32, device=dev)
