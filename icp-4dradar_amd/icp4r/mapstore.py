@@ -28,11 +28,14 @@ RADAR_RADIUS = 80.0  # radar_odometry.cpp:36
 class KD_TREE:  # noqa: N801 — the reference's class name
     """ikd-Tree replacement for radar_odometry's map: a dense device store in insertion order with
     Sector_Search, Box_Search and Radius_Search as full filters, box deletion and the downsampling
-    insert (ikd-Tree's rebuild / rebalancing change no result and have no counterpart)."""
+    insert.  ikd-Tree's rebuild / rebalancing have no counterpart; the one result they touch is the
+    reference's Sector_Search after a deletion or a downsampling add, which may also return lazily
+    deleted points with |dh| > 300 until a rebuild drops them — this store never does
+    (include/icp4r/icp4r_map.h)."""
 
     def __init__(self, delete_param: float = 0.5, balance_param: float = 0.6, box_length: float | None = None,
                  ctx: Context | None = None):
-        # delete/balance parameters steer ikd-Tree's rebalancing, which does not change query results;
+        # delete/balance parameters steer ikd-Tree's rebalancing, which has no counterpart here;
         # box_length is the downsample box of Add_Points(.., True) (the node adds with downsample_on = false).
         # A tree that was never given a box (constructor or set_downsample_param) shows ikd-Tree's default
         # of 0.2 but refuses Add_Points(.., True), as every tree did before the downsampling insert existed.

@@ -30,7 +30,15 @@
  * half-open in float, min[k] <= p[k] && max[k] > p[k]; radius membership is calc_dist(p, c) <=
  * fl(r * r); a NaN coordinate or bound fails every comparison, so such a point is never found and
  * never deleted.  Deleting leaves the survivors dense and in insertion order.  ikd-Tree's rebuild
- * and rebalancing do not change any result and have no counterpart here.
+ * and rebalancing have no counterpart here.  They change no result of Box_Search or Radius_Search,
+ * and none of Sector_Search while nothing has been deleted (the node never deletes).  After a
+ * deletion or a downsampling add, however, the reference's Sector_Search may also return deleted
+ * points with |dh| > 300: its keep test reads `!deleted && d2 <= r*r && dh < 60 || dh > 300`, so the
+ * second branch ignores the flag, and a lazily deleted node stays in the tree until a rebuild
+ * happens to drop it.  Which of them come back depends on the tree's rebalancing state; the store
+ * compacts and never returns a deleted point (tests/test_map_reference.py, cases G1 and G2).
+ * KD_TREE::size() differs in the same way: the reference counts lazily deleted nodes, the store
+ * counts the points it holds.
  */
 #ifndef ICP4R_MAP_H
 #define ICP4R_MAP_H

@@ -44,7 +44,7 @@ class KD_TREE {  // NOLINT — the reference's class name
     using PointVector = std::vector<PointType>;
 #endif
 
-    // delete / balance parameters steer ikd-Tree's rebalancing (no effect on query results);
+    // delete / balance parameters steer ikd-Tree's rebalancing (no counterpart here: icp4r_map.h);
     // box_length is the downsample box of Add_Points(.., true) (the node adds with false).
     explicit KD_TREE(float delete_param = 0.5f, float balance_param = 0.6f, float box_length = 0.2f)
         : delete_param_(delete_param), balance_param_(balance_param), downsample_size_(box_length) {}

@@ -17,9 +17,15 @@
  * pre-order traversal of its current (rebalanced) tree; the restatement returns insertion order —
  * the SAME SET, in a defined order.
  *
- * Parity status: UNPINNED by the reference (no tests or fixtures for this path; ikd_Tree.cpp needs
- * PCL headers, absent here, so it is not built).  Pinned by analytic known-answer tests
- * (tests/test_map.py).  The only library function on the path is asinf (glibc here; ROCm ocml on
+ * Parity status: PINNED to the reference's own ikd-Tree.  `make ref` here compiles the reference's
+ * ikd_Tree.{h,cpp} against the PCL-1.8-shaped include tree of tests/cpp/pcl18 (ref/ikd_ref_driver.cpp,
+ * ikd_ref.py); tests/golden/ikd_sector.npz records the real tree's calc_heading / calc_dist bits and
+ * its Sector_Search sets over the node's loop, and tests/test_map_reference.py holds this file to
+ * them bit for bit, and runs the real tree live where it is built.  Also pinned by analytic
+ * known-answer tests (tests/test_map.py).  One thing is deliberately not restated: after a deletion
+ * or a downsampling add the real tree may also return lazily deleted points with |dh| > 300 (the
+ * `|| dh > 300` branch ignores the flag) until a rebuild drops them; `deleted` is 0 here.
+ * The only library function on the path is asinf (glibc here; ROCm ocml on
  * the device): the two may differ by an ulp, which can flip only points within ~1e-4 deg of a
  * sector edge (|dh| = 60 or 300) — the GPU tests allow exactly that, nothing else.
  */

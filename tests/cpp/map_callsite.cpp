@@ -10,7 +10,11 @@
 #include <fstream>
 #include <vector>
 
+#ifdef ICP4R_CALLSITE_REFERENCE_IKD_TREE  // oracle/Makefile, target ref: the reference's own header
+#include "ikd_Tree.h"
+#else
 #include "icp4r/ikd_compat.hpp"
+#endif
 
 #define RADAR_RADIUS 80  // radar_odometry.cpp:36
 

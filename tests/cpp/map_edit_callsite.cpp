@@ -12,7 +12,11 @@
 #include <limits>
 #include <vector>
 
+#ifdef ICP4R_CALLSITE_REFERENCE_IKD_TREE  // oracle/Makefile, target ref: the reference's own header
+#include "ikd_Tree.h"
+#else
 #include "icp4r/ikd_compat.hpp"
+#endif
 
 typedef pcl::PointXYZI PointType;
 typedef KD_TREE<PointType>::PointVector PointVector;
@@ -49,7 +53,7 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "short input\n");
         return 2;
     }
-    KD_TREE<PointType> tree(0.5, 0.6, 0.2);
+    static KD_TREE<PointType> tree(0.5, 0.6, 0.2);  // static: the reference's tree is about 64 MB by value
     tree.Build(build);
     tree.set_downsample_param(ds);
     const int counter = tree.Add_Points(add, true);
