@@ -1,6 +1,6 @@
 // icp4r_device.hpp — device-side helpers shared by the kernel translation units
-// (icp4r_index.hip, icp4r_kernels.hip, icp4r_gicp.hip): scalar-cache pointers, the XCD-aware work mapping, the
-// slotted work counters and the NN key.
+// (icp4r_index.hip, icp4r_kernels.hip, icp4r_gicp.hip, icp4r_map.hip, icp4r_map_knn.hip): scalar-cache pointers,
+// the XCD-aware work mapping, the slotted work counters, the NN key, the top-K lists and the map's distance.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -147,5 +147,54 @@ __device__ __forceinline__ float wave_maxf(float x) {
 // Box pruning is conservative in float: a box lower bound is shrunk by 2^-16 before its `<=` test
 // against a d², which covers the few-ulp rounding of both the bound and l2_simple.
 constexpr float kLbShrink = 1.0f - 1.0f / 65536.0f;
+
+// ---- exact k-NN lists (gicp_knn_cov_kernel, gicp_cov_kernel, map_knn_kernel)
+// insert key into the ascending top-K list (registers: a fully unrolled compare-exchange chain)
+template <int K>
+__device__ __forceinline__ void knn_insert(uint64_t (&best)[K], uint64_t key) {
+    if (key < best[K - 1]) {
+#pragma unroll
+        for (int s = 0; s < K; ++s) {
+            const uint64_t lo = key < best[s] ? key : best[s];
+            key = key < best[s] ? best[s] : key;
+            best[s] = lo;
+        }
+    }
+}
+
+// the L lists of a query (lanes lane ^ o, o < L) into one: each lane takes in its partners' keys, so all
+// L lanes end with the K smallest of their union
+template <int K, int L>
+__device__ __forceinline__ void knn_merge_lanes(uint64_t (&best)[K]) {
+#pragma unroll
+    for (int o = 1; o < L; o <<= 1) {
+        uint64_t other[K];
+#pragma unroll
+        for (int s = 0; s < K; ++s) {
+            const uint32_t lo = __shfl_xor((uint32_t)best[s], o, 64), hi = __shfl_xor((uint32_t)(best[s] >> 32), o, 64);
+            other[s] = (uint64_t)hi << 32 | lo;
+        }
+#pragma unroll
+        for (int s = 0; s < K; ++s) knn_insert<K>(best, other[s]);
+    }
+}
+
+// lower bound of the squared distance from (x, y, z) to the box [lo, hi] (fused; compare through kLbShrink)
+__device__ __forceinline__ float box_lb(const v4f lo, const v4f hi, float x, float y, float z) {
+    const float gx = fmaxf(fmaxf(lo.x - x, x - hi.x), 0.0f);
+    const float gy = fmaxf(fmaxf(lo.y - y, y - hi.y), 0.0f);
+    const float gz = fmaxf(fmaxf(lo.z - z, z - hi.z), 0.0f);
+    return __builtin_fmaf(gz, gz, __builtin_fmaf(gy, gy, gx * gx));
+}
+
+
+// KD_TREE::calc_dist (ikd_Tree.cpp:1427-1431): float, ((dx*dx + dy*dy) + dz*dz), unfused.
+__device__ __forceinline__ float map_calc_dist(float ax, float ay, float az, float bx, float by, float bz) {
+    const float dx = ax - bx, dy = ay - by, dz = az - bz;
+    float d = dx * dx;
+    d = d + dy * dy;
+    d = d + dz * dz;
+    return d;
+}
 
 }  // namespace icp4r

@@ -169,39 +169,9 @@ __device__ __forceinline__ void gicp_cov_from_knn(const uint64_t (&best)[K], int
     out[5] = o[8];
 }
 
-// insert key into the ascending top-K list (registers: a fully unrolled compare-exchange chain)
-template <int K>
-__device__ __forceinline__ void knn_insert(uint64_t (&best)[K], uint64_t key) {
-    if (key < best[K - 1]) {
-#pragma unroll
-        for (int s = 0; s < K; ++s) {
-            const uint64_t lo = key < best[s] ? key : best[s];
-            key = key < best[s] ? best[s] : key;
-            best[s] = lo;
-        }
-    }
-}
-
 // ---- covariances
 constexpr int kCovWG = 256;
 constexpr int kCovTile = 1024;
-
-// the L lists of a query (lanes lane ^ o, o < L) into one: each lane takes in its partners' keys, so all
-// L lanes end with the K smallest of their union
-template <int K, int L>
-__device__ __forceinline__ void knn_merge_lanes(uint64_t (&best)[K]) {
-#pragma unroll
-    for (int o = 1; o < L; o <<= 1) {
-        uint64_t other[K];
-#pragma unroll
-        for (int s = 0; s < K; ++s) {
-            const uint32_t lo = __shfl_xor((uint32_t)best[s], o, 64), hi = __shfl_xor((uint32_t)(best[s] >> 32), o, 64);
-            other[s] = (uint64_t)hi << 32 | lo;
-        }
-#pragma unroll
-        for (int s = 0; s < K; ++s) knn_insert<K>(best, other[s]);
-    }
-}
 
 // Brute-force exact k-NN (every point of the cloud through LDS tiles), L lanes per query each taking
 // every L-th point of a tile: plans that do not prune, and the reference the pruned walk is tested
@@ -246,13 +216,6 @@ __global__ __launch_bounds__(kCovWG) void gicp_cov_kernel(const float4* __restri
 // Keys are (d², index): the K smallest are exactly the brute-force set, ties to the lowest index.
 // (L = 1 had one wave walk ~25 blocks of 16 points one after another for 64 queries, ~400 distance
 // evaluations per query on the bench clouds: latency-bound, a wave per SIMD on a single 8k cloud.)
-__device__ __forceinline__ float box_lb(const v4f lo, const v4f hi, float x, float y, float z) {
-    const float gx = fmaxf(fmaxf(lo.x - x, x - hi.x), 0.0f);
-    const float gy = fmaxf(fmaxf(lo.y - y, y - hi.y), 0.0f);
-    const float gz = fmaxf(fmaxf(lo.z - z, z - hi.z), 0.0f);
-    return __builtin_fmaf(gz, gz, __builtin_fmaf(gy, gy, gx * gx));
-}
-
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));

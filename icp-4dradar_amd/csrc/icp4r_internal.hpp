@@ -329,6 +329,55 @@ hipError_t launch_downsample(const float4* map, int64_t n0, const float4* arr, i
                              int32_t* counts, int32_t* offsets, int32_t* total, float4* out, int32_t** counter,
                              hipStream_t st);
 
+// Stable LSD radix sort of n (key, value) pairs by the key's low `bits` bits (8 per pass), between a
+// and b; -> the buffer that holds the result.  counts / offsets: 256 * sector_blocks(n) entries.
+int2* launch_radix_sort(int2* a, int2* b, int32_t n, int bits, int32_t* counts, int32_t* offsets, int32_t* total,
+                        hipStream_t st);
+
+// ---- the map's k-NN index and search (icp4r_map_knn.hip)
+// A snapshot of the first `indexed` stored points: their float4 copy in Morton order (.w = the bits of
+// the insertion position; a point with a non-finite coordinate, and the padding up to a whole leaf,
+// hold NaN coordinates), boxes of the leaves (16 consecutive positions) and, above them, of every 64
+// consecutive nodes of the level below, until a level has at most 64 nodes (or kKnnMaxLevels).
+constexpr int kKnnLeaf = 16, kKnnFan = 64, kKnnMaxLevels = 4;
+struct KnnIndex {
+    const float4* sorted = nullptr;
+    const float4* box[kKnnMaxLevels] = {};  // per level: (lo, hi) per node; level 0 = the leaves
+    int32_t cnt[kKnnMaxLevels] = {};        // nodes per level
+    int32_t levels = 0;                     // 0: no tree (nothing indexed)
+    const uint32_t* bbox = nullptr;         // the finite points' bounding box, 6 order-preserving words
+};
+struct KnnLayout {  // byte offsets into the index buffer
+    size_t sorted, box[kKnnMaxLevels], bbox, bytes;
+    int32_t cnt[kKnnMaxLevels], levels;
+};
+KnnLayout knn_layout(int64_t n);
+// Scratch of a sort of n pairs: two pair buffers, the radix counts and offsets, one int32.
+struct KnnSortLayout {
+    size_t pa, pb, counts, offsets, total, bytes;
+};
+KnnSortLayout knn_sort_layout(int64_t n);
+// Builds the index of pts[0, n) (0 < n < 2^31) into `index` (knn_layout(n).bytes) with `scratch`
+// (knn_sort_layout(n).bytes).
+hipError_t launch_knn_index(const float4* pts, int64_t n, void* index, void* scratch, hipStream_t st);
+KnnIndex knn_view(const void* index, int64_t n);
+struct KnnSearch {
+    const float4* pts;   // the store
+    int64_t n;
+    KnnIndex ix;         // the tree over [0, tail0) (levels = 0: none)
+    int64_t tail0;       // [tail0, n) is swept through LDS tiles
+    const float4* q;     // device queries
+    int32_t nq, k;
+    double md2;          // max_dist * max_dist
+    float bound;         // md2 rounded up to float (-inf: nothing can match)
+    float4* pout;        // any output may be null
+    float* dout;
+    int32_t* iout;
+    int32_t* fout;
+};
+// scratch (knn_sort_layout(nq).bytes) sorts the queries by the index's Morton key; unused without a tree
+hipError_t launch_knn_search(const KnnSearch& s, void* scratch, hipStream_t st);
+
 // ---- radar ego velocity (icp4r_ego.hip)
 struct EgoArgs {
     const float* rec;      // device records, 5 floats each

@@ -12,6 +12,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "icp4r_device.hpp"
 #include "icp4r_internal.hpp"
 
 namespace icp4r {
@@ -20,15 +21,6 @@ constexpr int kSecWG = 256;
 constexpr int kSecPer = 16;                  // points per thread
 constexpr int kSecBlock = kSecWG * kSecPer;  // points per workgroup
 constexpr double kPi = 3.14159265358979323846;  // glibc's M_PI (math.h), the reference's constant
-
-// KD_TREE::calc_dist (ikd_Tree.cpp:1427-1431): float, ((dx*dx + dy*dy) + dz*dz), unfused.
-__device__ __forceinline__ float map_calc_dist(float ax, float ay, float az, float bx, float by, float bz) {
-    const float dx = ax - bx, dy = ay - by, dz = az - bz;
-    float d = dx * dx;
-    d = d + dy * dy;
-    d = d + dz * dz;
-    return d;
-}
 
 // KD_TREE::calc_heading (ikd_Tree.cpp:1434-1448): float asinf / sqrtf (ikd_Tree.h's `using namespace
 // std` picks the float overloads), `* 180` in float, `/ M_PI` and `180 +` in double, stored as float.
@@ -418,6 +410,24 @@ __global__ __launch_bounds__(kSecWG) void ds_radix_scatter_kernel(const int2* __
     }
 }
 
+// Sorts n (key, value) pairs by the low `bits` bits of the key, stably, 8 bits per pass, ping-ponging
+// between a and b; -> the buffer that holds the result.  counts / offsets: 256 * sector_blocks(n)
+// entries each; total: one int32 the scans write.
+int2* launch_radix_sort(int2* a, int2* b, int32_t n, int bits, int32_t* counts, int32_t* offsets, int32_t* total,
+                        hipStream_t st) {
+    const int32_t nblk = (int32_t)sector_blocks(n);
+    for (int shift = 0; shift < bits; shift += 8) {
+        hipLaunchKernelGGL(ds_radix_count_kernel, dim3((unsigned)nblk), dim3(kSecWG), 0, st, a, n, shift, nblk, counts);
+        hipLaunchKernelGGL(sector_scan_kernel, dim3(1), dim3(1024), 0, st, counts, 256 * nblk, offsets, total);
+        hipLaunchKernelGGL(ds_radix_scatter_kernel, dim3((unsigned)nblk), dim3(kSecWG), 0, st, a, b, n, shift, nblk,
+                           offsets);
+        int2* t = a;
+        a = b;
+        b = t;
+    }
+    return a;
+}
+
 // KD_TREE::same_point (ikd_Tree.cpp:1422-1423): float fabs against the double 1e-6.
 __device__ __forceinline__ bool ds_same_point(const float4 a, const float4 b) {
     return (double)fabsf(a.x - b.x) < 1e-6 && (double)fabsf(a.y - b.y) < 1e-6 && (double)fabsf(a.z - b.z) < 1e-6;
@@ -539,17 +549,7 @@ hipError_t launch_downsample(const float4* map, int64_t n0, const float4* arr, i
     if (n0 > 0)
         hipLaunchKernelGGL(ds_stored_kernel, dim3((unsigned)((n0 + 255) / 256)), dim3(256), 0, st, map, (int32_t)n0, arr,
                            ds, rep, mask, scount, smin, sslot);
-    const int32_t nblk = (int32_t)sector_blocks(na);
-    for (int shift = 0; shift < bits + 1; shift += 8) {  // slots 0 .. size: bits + 1 key bits
-        hipLaunchKernelGGL(ds_radix_count_kernel, dim3((unsigned)nblk), dim3(kSecWG), 0, st, pa, (int32_t)na, shift, nblk,
-                           rcounts);
-        hipLaunchKernelGGL(sector_scan_kernel, dim3(1), dim3(1024), 0, st, rcounts, 256 * nblk, roffsets, cnt + 1);
-        hipLaunchKernelGGL(ds_radix_scatter_kernel, dim3((unsigned)nblk), dim3(kSecWG), 0, st, pa, pb, (int32_t)na, shift,
-                           nblk, roffsets);
-        int2* t = pa;
-        pa = pb;
-        pb = t;
-    }
+    pa = launch_radix_sort(pa, pb, (int32_t)na, bits + 1, rcounts, roffsets, cnt + 1, st);  // slots 0 .. size: bits + 1 key bits
     hipLaunchKernelGGL(ds_walk_kernel, dim3(ga), dim3(256), 0, st, pa, (int32_t)na, size, map, arr, ds, scount, smin, swin,
                        akeep, cnt);
     if ((e = hipGetLastError()) != hipSuccess) return e;

@@ -78,6 +78,10 @@ MAP_EXPORTED_SYMBOLS = [
     "icp4r_map_add_points_downsample", "icp4r_map_delete_boxes", "icp4r_map_box_search", "icp4r_map_radius_search",
     "icp4r_map_box_search_device", "icp4r_map_radius_search_device",
 ]
+# include/icp4r/icp4r_map_knn.h (the store's Nearest_Search and its index)
+MAP_KNN_EXPORTED_SYMBOLS = [
+    "icp4r_map_nearest_search", "icp4r_map_nearest_search_device", "icp4r_map_index_build", "icp4r_map_index_stats",
+]
 
 
 def status_name(code: int) -> str:
@@ -207,6 +211,11 @@ def load():
         "icp4r_map_radius_search": (C.c_int, [vp, vp, C.c_float, vp, i64, C.POINTER(i64)]),
         "icp4r_map_box_search_device": (C.c_int, [vp, vp, vp, vp, vp]),
         "icp4r_map_radius_search_device": (C.c_int, [vp, vp, C.c_float, vp, vp, vp]),
+        # icp4r_map_knn.h
+        "icp4r_map_nearest_search": (C.c_int, [vp, vp, i64, i32, i32, C.c_double, i32, vp, vp, vp, vp]),
+        "icp4r_map_nearest_search_device": (C.c_int, [vp, vp, i64, i32, C.c_double, i32, vp, vp, vp, vp, vp]),
+        "icp4r_map_index_build": (C.c_int, [vp]),
+        "icp4r_map_index_stats": (C.c_int, [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i32)]),
         # icp4r_multi.h
         "icp4r_shard": (C.c_int, [i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]),
         "icp4r_align_batch_multi": (C.c_int, [C.POINTER(vp), i32, vp, vp, vp, vp, vp, vp, i32, vp, C.POINTER(Params),

@@ -7,8 +7,8 @@ reference's radar_odometry node uses:
     pointAssociateToMap(...); ikd_Tree.Add_Points(.., false) :382-390
     ikd_Tree.Sector_Search(p_now, RADAR_RADIUS, heading, SubMap->points)   :396
 
-and ikd-Tree's map-maintenance calls (ikd_Tree.h:238-245): Delete_Point_Boxes, Box_Search,
-Radius_Search and the downsampling Add_Points(points, True).
+and ikd-Tree's map-maintenance calls (ikd_Tree.h:238-245): Nearest_Search, Delete_Point_Boxes,
+Box_Search, Radius_Search and the downsampling Add_Points(points, True).
 
 Same method names; clouds are (N, >=3) float32 arrays (x, y, z[, intensity]).  Device-resident and
 GPU-only: there is no CPU fallback (the library raises if it is missing).  A tree may outlive its
@@ -23,12 +23,15 @@ import numpy as np
 from . import E_INVALID, Context, ICP4RError, _check, _cloud, _ptr, default_context, load
 
 RADAR_RADIUS = 80.0  # radar_odometry.cpp:36
+KNN_MAX_K = 32  # ICP4R_MAP_KNN_MAX_K
+KNN_BRUTE = 1   # ICP4R_MAP_KNN_BRUTE: every stored point, no index
+KNN_INDEX = 2   # ICP4R_MAP_KNN_INDEX: the index whatever the map's size
 
 
 class KD_TREE:  # noqa: N801 — the reference's class name
     """ikd-Tree replacement for radar_odometry's map: a dense device store in insertion order with
-    Sector_Search, Box_Search and Radius_Search as full filters, box deletion and the downsampling
-    insert.  ikd-Tree's rebuild / rebalancing have no counterpart; the one result they touch is the
+    Sector_Search, Box_Search and Radius_Search as full filters, box deletion, the downsampling
+    insert, and an exact batched Nearest_Search over a Morton-order index the store keeps of itself.  ikd-Tree's rebuild / rebalancing have no counterpart; the one result they touch is the
     reference's Sector_Search after a deletion or a downsampling add, which may also return lazily
     deleted points with |dh| > 300 until a rebuild drops them — this store never does
     (include/icp4r/icp4r_map.h)."""
@@ -120,6 +123,41 @@ class KD_TREE:  # noqa: N801 — the reference's class name
                                                  C.byref(k)), "icp4r_map_sector_search")
         return out[:k.value].copy()
 
+    def Nearest_Search(self, point, k_nearest: int, max_dist: float = float("inf")):  # noqa: N802
+        """The reference's call for one point: (points (K', 4), squared distances (K',)), nearest first,
+        K' = min(k_nearest, stored points within max_dist).  One call pays a launch and a
+        synchronisation: hand a whole scan to nearest_search instead."""
+        q = np.asarray(point, np.float32).reshape(-1)[:3].reshape(1, 3)
+        pts, dist, _, found = self.nearest_search(q, k_nearest, max_dist)
+        return pts[0, :found[0]].copy(), dist[0, :found[0]].copy()
+
+    def nearest_search(self, queries, k: int, max_dist: float = float("inf"), brute: bool = False, flags: int = 0):
+        """Batched Nearest_Search: the k nearest stored points of every query (include/icp4r/icp4r_map.h).
+        -> points (nq, k, 4) float32, squared distances (nq, k) float32, insertion positions (nq, k) int32
+        and found (nq,) int32; a row's unused slots hold a zero point, +inf and -1.  brute: no index."""
+        a, nq, stride = _cloud(queries)
+        kk = max(int(k), 0)
+        pts = np.empty((nq, kk, 4), np.float32)
+        dist = np.empty((nq, kk), np.float32)
+        idx = np.empty((nq, kk), np.int32)
+        found = np.empty((nq,), np.int32)
+        _check(self._lib.icp4r_map_nearest_search(self._h, _ptr(a), nq, stride, int(k), float(max_dist),
+                                                  int(flags) | (KNN_BRUTE if brute else 0), _ptr(pts), _ptr(dist),
+                                                  _ptr(idx), _ptr(found)), "icp4r_map_nearest_search")
+        return pts, dist, idx, found
+
+    def index_build(self):
+        """Brings the k-NN index up to date now (a search does so by itself when it has to)."""
+        _check(self._lib.icp4r_map_index_build(self._h), "icp4r_map_index_build")
+
+    def index_stats(self) -> dict:
+        """indexed: points the index covers; tail: appended since; tail_limit: the tail past which the next
+        search rebuilds; builds: index builds so far."""
+        a, b, c, d = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int32()
+        _check(self._lib.icp4r_map_index_stats(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)),
+               "icp4r_map_index_stats")
+        return {"indexed": a.value, "tail": b.value, "tail_limit": c.value, "builds": d.value}
+
     def size(self) -> int:
         n = C.c_int64()
         _check(self._lib.icp4r_map_size(self._h, C.byref(n)), "icp4r_map_size")
@@ -156,6 +194,14 @@ class KD_TREE:  # noqa: N801 — the reference's class name
         _check(self._lib.icp4r_map_radius_search_device(self._h, _ptr(c), float(radius), C.c_void_p(d_out),
                                                         C.c_void_p(d_count), C.c_void_p(stream) if stream else None),
                "icp4r_map_radius_search_device")
+
+    def nearest_search_device(self, d_queries: int, nq: int, k: int, max_dist: float = float("inf"), d_points: int = 0,
+                              d_dist: int = 0, d_index: int = 0, d_found: int = 0, stream=None, flags: int = 0):
+        """nq float4 queries at device address d_queries; any of the four device outputs may be 0."""
+        vp = lambda x: C.c_void_p(x) if x else None  # noqa: E731
+        _check(self._lib.icp4r_map_nearest_search_device(self._h, vp(d_queries), nq, int(k), float(max_dist), int(flags),
+                                                         vp(d_points), vp(d_dist), vp(d_index), vp(d_found),
+                                                         vp(stream)), "icp4r_map_nearest_search_device")
 
     def points_device(self) -> tuple[int, int]:
         p, n = C.c_void_p(), C.c_int64()

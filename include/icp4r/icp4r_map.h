@@ -39,6 +39,25 @@
  * compacts and never returns a deleted point (tests/test_map_reference.py, cases G1 and G2).
  * KD_TREE::size() differs in the same way: the reference counts lazily deleted nodes, the store
  * counts the points it holds.
+ *
+ * Nearest_Search (ikd_Tree.h:238, ikd_Tree.cpp:368-398 and :877-1021; its entries are declared in
+ * icp4r/icp4r_map_knn.h, which this header includes) is the one query with an index behind it.  For a query q and the stored points p_i (i = the insertion position, as
+ * icp4r_map_points_device shows it), d_i = calc_dist(q, p_i) in float, ((dx*dx) + dy*dy) + dz*dz
+ * unfused; p_i is a candidate iff its three coordinates are finite and (double)d_i <= max_dist *
+ * max_dist (the product in double: a negative max_dist acts as its magnitude, a NaN finds nothing, a
+ * d_i that overflowed to +inf passes an infinite max_dist).  The answer is the min(k, #candidates)
+ * smallest candidates by (d_i, i), ascending, each with its point, d_i and i.  A query with a
+ * non-finite coordinate finds nothing.  The reference's tree gives the same distances (an exact
+ * k-NN that never returns a lazily deleted node); among exactly equal d_i it keeps whichever its
+ * traversal met first where the store keeps the lowest i, a stored point with a non-finite
+ * coordinate is never returned (the reference's Build over NaN has no defined order), and k < 1,
+ * undefined in the reference, is refused here as is k > ICP4R_MAP_KNN_MAX_K.
+ *
+ * The index is a snapshot the map owns: the points in Morton order with a 64-ary tree of boxes over
+ * blocks of 16.  Build, Delete_Point_Boxes, the downsampling insert and growth of the store drop it;
+ * a plain append (Add_Points(.., false), add_scan) leaves it and the appended points form a tail
+ * that the search sweeps by brute force, until the tail would pass tail_limit and the next search
+ * rebuilds the index.
  */
 #ifndef ICP4R_MAP_H
 #define ICP4R_MAP_H
@@ -116,7 +135,7 @@ int icp4r_map_radius_search_device(icp4r_map* map, const float* center, float ra
  * insert, growth) moves them. */
 int icp4r_map_points_device(icp4r_map* map, const float** d_points, int64_t* n);
 
-/* Average device time (HIP events) of the search, delete and downsampled-insert launches since the
+/* Average device time (HIP events) of the search, delete, downsampled-insert and index-build launches since the
  * last icp4r_map_time_reset, and how many there were. */
 int icp4r_map_time_ms(icp4r_map* map, double* avg_ms, int32_t* calls);
 int icp4r_map_time_reset(icp4r_map* map);
@@ -124,5 +143,9 @@ int icp4r_map_time_reset(icp4r_map* map);
 #ifdef __cplusplus
 }
 #endif
+
+/* KD_TREE::Nearest_Search and the map's index: icp4r_map_nearest_search[_device],
+ * icp4r_map_index_build, icp4r_map_index_stats. */
+#include "icp4r/icp4r_map_knn.h"
 
 #endif /* ICP4R_MAP_H */

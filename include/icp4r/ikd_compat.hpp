@@ -8,7 +8,9 @@
 // and links libicp4r.so; `KD_TREE<pcl::PointXYZI> ikd_Tree(0.3, 0.6, 0.5);` and the Build /
 // set_downsample_param / Add_Points / Sector_Search calls stay textually unchanged.
 // ikd-Tree's map-maintenance calls carry the reference's signatures too (ikd_Tree.h:238-245):
-// Delete_Point_Boxes, Box_Search, Radius_Search, Add_Points(.., true) and BoxPointType.
+// Nearest_Search, Delete_Point_Boxes, Box_Search, Radius_Search, Add_Points(.., true) and BoxPointType.
+// One Nearest_Search per point pays a launch and a synchronisation each: a port should hand a whole
+// scan to Nearest_Search_Batch.
 //
 // Semantics (include/icp4r/icp4r_map.h): a dense device store in insertion order; Sector_Search,
 // Box_Search and Radius_Search are full filters with the reference's keep tests, returning the same
@@ -19,6 +21,7 @@
 // namespace-scope tree, as the node declares it, outlives nothing it depends on.
 #pragma once
 
+#include <cmath>
 #include <cstdint>
 #include <stdexcept>
 #include <string>
@@ -112,6 +115,40 @@ class KD_TREE {  // NOLINT — the reference's class name
         search(Storage, "Sector_Search", [&](float* out, int64_t cap, int64_t* k) {
             return icp4r_map_sector_search(map(), c, radius, heading, out, cap, k);
         });
+    }
+
+    // The reference's call: the k_nearest stored points nearest to `point` within max_dist, nearest
+    // first, and their squared distances (exact; ties to the earliest inserted: icp4r_map.h).
+    void Nearest_Search(PointType point, int k_nearest, PointVector& Nearest_Points,  // NOLINT
+                        std::vector<float>& Point_Distance, double max_dist = INFINITY) {
+        std::vector<PointType> one(1, point);
+        std::vector<int> found;
+        Nearest_Search_Batch(one, k_nearest, Nearest_Points, Point_Distance, found, max_dist);
+        Nearest_Points.resize((size_t)found[0]);
+        Point_Distance.resize((size_t)found[0]);
+    }
+
+    // The same for a whole scan in one launch: row q of Nearest_Points / Point_Distance (k_nearest
+    // slots each) holds found[q] answers, nearest first; the unused slots hold a zero point and +inf.
+    template <typename Vec, typename OutVec>
+    void Nearest_Search_Batch(const Vec& points, int k_nearest, OutVec& Nearest_Points,  // NOLINT
+                              std::vector<float>& Point_Distance, std::vector<int>& found, double max_dist = INFINITY) {
+        const size_t nq = points.size(), rows = nq * (size_t)(k_nearest > 0 ? k_nearest : 0);
+        std::vector<float> q = pack(points), out(rows * 4 + 4);
+        std::vector<int32_t> cnt(nq + 1);
+        Point_Distance.assign(rows, 0.0f);
+        check(icp4r_map_nearest_search(map(), q.data(), (int64_t)nq, 16, k_nearest, max_dist, 0, out.data(),
+                                       rows ? Point_Distance.data() : nullptr, nullptr, cnt.data()),
+              "Nearest_Search");
+        Nearest_Points.resize(rows);
+        for (size_t i = 0; i < rows; ++i) {
+            PointType& p = Nearest_Points[i];
+            p.x = out[4 * i];
+            p.y = out[4 * i + 1];
+            p.z = out[4 * i + 2];
+            p.intensity = out[4 * i + 3];
+        }
+        found.assign(cnt.begin(), cnt.begin() + (std::ptrdiff_t)nq);
     }
 
     int size() {
