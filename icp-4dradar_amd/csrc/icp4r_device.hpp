@@ -197,4 +197,18 @@ __device__ __forceinline__ float map_calc_dist(float ax, float ay, float az, flo
     return d;
 }
 
+// x, y and z finite (false for NaN)
+__device__ __forceinline__ bool finite_xyz(const float4 p) {
+    return fabsf(p.x) < INFINITY && fabsf(p.y) < INFINITY && fabsf(p.z) < INFINITY;
+}
+
+// float <-> uint32 with the floats' order, for integer atomicMin / atomicMax (launch_finite_bbox)
+__device__ __forceinline__ uint32_t float_ord(float f) {
+    const uint32_t u = __float_as_uint(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float float_unord(uint32_t u) {
+    return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
+}
+
 }  // namespace icp4r

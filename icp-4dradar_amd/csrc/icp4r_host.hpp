@@ -92,6 +92,8 @@ namespace icp4r_host {
 // map's device memory and events and leaves it detached (ctx = nullptr, empty) — every entry on it
 // then fails with ICP4R_E_INVALID and icp4r_map_destroy only deletes the host struct
 void map_detach(icp4r_map* m);
+// the context a live map was created on (nullptr: detached)
+icp4r_ctx* map_context(const icp4r_map* m);
 }  // namespace icp4r_host
 
 struct icp4r_ctx {
@@ -135,4 +137,8 @@ struct icp4r_ctx {
     // pair of each; 0 pairs: none, or overwritten since): icp4r__test_gicp_covariances reads them back
     int gicp_last_pairs = 0;
     int64_t gicp_last_xs = 0, gicp_last_ts = 0;
+    // voxel-grid filter (icp4r_voxel.cpp): workspace, the host entries' staging, one event pair per launch
+    icp4r_host::DevBuf vox_work, vox_in, vox_out, vox_cnt;
+    std::vector<icp4r_host::EventPair> vox_events;
+    size_t vox_used = 0;
 };

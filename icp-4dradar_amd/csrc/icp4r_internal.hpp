@@ -334,6 +334,38 @@ hipError_t launch_downsample(const float4* map, int64_t n0, const float4* arr, i
 int2* launch_radix_sort(int2* a, int2* b, int32_t n, int bits, int32_t* counts, int32_t* offsets, int32_t* total,
                         hipStream_t st);
 
+// The compactions' exclusive scan of nblk block counts by one workgroup; their sum to *total.
+hipError_t launch_block_scan(const int32_t* counts, int nblk, int32_t* offsets, int32_t* total, hipStream_t st);
+// The bounding box of the points of pts[0, n) whose x, y and z are finite: bbox[0..2] = min, bbox[3..5] =
+// max as order-preserving words (float_unord, icp4r_device.hpp), reduced with integer atomics; no such
+// point leaves min = +inf, max = -inf.  Shared by the k-NN index and the voxel grid.
+hipError_t launch_finite_bbox(const float4* pts, int64_t n, uint32_t* bbox, hipStream_t st);
+
+// ---- voxel-grid downsampling (icp4r_voxel.hip; include/icp4r/icp4r_voxel.h)
+struct VoxelArgs {
+    float inv[3];        // 1.0f / leaf, correctly rounded
+    int32_t all_data;    // 0: the output intensity is 0
+    uint32_t min_pts;    // voxels with fewer members give no output
+};
+// What voxel_grid_kernel leaves on the device (and the host entry reads back).
+struct VoxelGridDev {
+    int32_t min_b[3];
+    int32_t div[3];
+    int32_t flag;        // 0: a grid; 1: no participating point; -1: grid overflow
+    int32_t pad;
+};
+struct VoxelLayout {  // byte offsets into the workspace
+    size_t bbox, grid, tot, pa, pb, counts, offsets, heads, kept, bytes;
+};
+VoxelLayout voxel_layout(int64_t n);
+// Stage 1: the bounding box and the grid of pts[0, n) (0 < n < 2^31) into the workspace.
+hipError_t launch_voxel_grid(const float4* pts, int64_t n, const VoxelArgs& a, void* work, hipStream_t st);
+// Stage 2, after stage 1 on the same stream: keys, sort by the key's low `bits` bits (31: any grid; the
+// host entry passes the grid's own width), voxels, centroids.  out: room for n points; *count: the
+// voxels written, or -1 on grid overflow (nothing written then).
+hipError_t launch_voxel_filter(const float4* pts, int64_t n, const VoxelArgs& a, int bits, void* work, float4* out,
+                               int32_t* count, hipStream_t st);
+
 // ---- the map's k-NN index and search (icp4r_map_knn.hip)
 // A snapshot of the first `indexed` stored points: their float4 copy in Morton order (.w = the bits of
 // the insertion position; a point with a non-finite coordinate, and the padding up to a whole leaf,

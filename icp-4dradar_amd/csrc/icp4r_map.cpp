@@ -332,6 +332,8 @@ void map_detach(icp4r_map* m) {
     m->ctx = nullptr;
 }
 
+icp4r_ctx* map_context(const icp4r_map* m) { return m->ctx; }
+
 }  // namespace icp4r_host
 
 extern "C" {

@@ -168,6 +168,64 @@ __global__ __launch_bounds__(1024) void sector_scan_kernel(const int32_t* __rest
     if (tid == 0) *total = carry;
 }
 
+// The same exclusive scan for long inputs (the radix sort's 256 counts per block: 410 k entries at
+// 6.5 M pairs, where tiles of 1024 cost 400 rounds of three barriers): a thread takes 8 consecutive
+// entries per round, so a round covers 8192.
+constexpr int kScanPer = 8;  // (the 16-byte accesses below spell out 8)
+__global__ __launch_bounds__(1024) void wide_scan_kernel(const int32_t* __restrict__ counts, int nblk,
+                                                         int32_t* __restrict__ offsets, int32_t* __restrict__ total) {
+    __shared__ int32_t wsum[16];
+    __shared__ int32_t carry;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid == 0) carry = 0;
+    __syncthreads();
+    const bool vec = ((reinterpret_cast<uintptr_t>(counts) | reinterpret_cast<uintptr_t>(offsets)) & 15) == 0;
+    for (int b0 = 0; b0 < nblk; b0 += 1024 * kScanPer) {
+        const int i0 = b0 + tid * kScanPer;
+        const bool whole = vec && i0 + kScanPer <= nblk;  // two 16-byte accesses instead of eight of 4
+        int v[kScanPer], t = 0;
+        if (whole) {
+            const int4 a = reinterpret_cast<const int4*>(counts + i0)[0], b = reinterpret_cast<const int4*>(counts + i0)[1];
+            v[0] = a.x, v[1] = a.y, v[2] = a.z, v[3] = a.w, v[4] = b.x, v[5] = b.y, v[6] = b.z, v[7] = b.w;
+        } else {
+#pragma unroll
+            for (int e = 0; e < kScanPer; ++e) v[e] = i0 + e < nblk ? counts[i0 + e] : 0;
+        }
+#pragma unroll
+        for (int e = 0; e < kScanPer; ++e) t += v[e];
+        int incl = t;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int o = __shfl_up(incl, off, 64);
+            if (lane >= off) incl += o;
+        }
+        if (lane == 63) wsum[wave] = incl;
+        __syncthreads();
+        int wbase = 0;
+        for (int w = 0; w < wave; ++w) wbase += wsum[w];
+        const int c0 = carry;
+        int run = c0 + wbase + incl - t;
+        int x[kScanPer];
+#pragma unroll
+        for (int e = 0; e < kScanPer; ++e) {
+            x[e] = run;
+            run += v[e];
+        }
+        if (whole) {
+            reinterpret_cast<int4*>(offsets + i0)[0] = make_int4(x[0], x[1], x[2], x[3]);
+            reinterpret_cast<int4*>(offsets + i0)[1] = make_int4(x[4], x[5], x[6], x[7]);
+        } else {
+#pragma unroll
+            for (int e = 0; e < kScanPer; ++e)
+                if (i0 + e < nblk) offsets[i0 + e] = x[e];
+        }
+        __syncthreads();
+        if (tid == 1023) carry = c0 + wbase + incl;
+        __syncthreads();
+    }
+    if (tid == 0) *total = carry;
+}
+
 // Ordered write: within a block, round k covers 256 consecutive points, wave w its 64, lane its one
 // — so ranks taken round by round, wave by wave, lane by lane are insertion order.
 template <class Pred>
@@ -418,7 +476,7 @@ int2* launch_radix_sort(int2* a, int2* b, int32_t n, int bits, int32_t* counts, 
     const int32_t nblk = (int32_t)sector_blocks(n);
     for (int shift = 0; shift < bits; shift += 8) {
         hipLaunchKernelGGL(ds_radix_count_kernel, dim3((unsigned)nblk), dim3(kSecWG), 0, st, a, n, shift, nblk, counts);
-        hipLaunchKernelGGL(sector_scan_kernel, dim3(1), dim3(1024), 0, st, counts, 256 * nblk, offsets, total);
+        hipLaunchKernelGGL(wide_scan_kernel, dim3(1), dim3(1024), 0, st, counts, 256 * nblk, offsets, total);
         hipLaunchKernelGGL(ds_radix_scatter_kernel, dim3((unsigned)nblk), dim3(kSecWG), 0, st, a, b, n, shift, nblk,
                            offsets);
         int2* t = a;
@@ -426,6 +484,59 @@ int2* launch_radix_sort(int2* a, int2* b, int32_t n, int bits, int32_t* counts, 
         b = t;
     }
     return a;
+}
+
+hipError_t launch_block_scan(const int32_t* counts, int nblk, int32_t* offsets, int32_t* total, hipStream_t st) {
+    hipLaunchKernelGGL(wide_scan_kernel, dim3(1), dim3(1024), 0, st, counts, nblk, offsets, total);
+    return hipGetLastError();
+}
+
+// bbox[0..2] = min, bbox[3..5] = max over the finite points (set to all-ones / zero beforehand; no
+// finite point leaves min = +inf, max = -inf).
+__global__ __launch_bounds__(256) void finite_bbox_kernel(const float4* __restrict__ pts, int64_t n,
+                                                          uint32_t* __restrict__ bbox) {
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const float4 p = pts[i];
+        if (finite_xyz(p)) {
+            lo[0] = fminf(lo[0], p.x), hi[0] = fmaxf(hi[0], p.x);
+            lo[1] = fminf(lo[1], p.y), hi[1] = fmaxf(hi[1], p.y);
+            lo[2] = fminf(lo[2], p.z), hi[2] = fmaxf(hi[2], p.z);
+        }
+    }
+    // Waves -> workgroup through LDS, then one atomic per word, and only where it can still move the
+    // word: every wave of a launch hitting the same six words costs ~10 ns per atomic at one L2
+    // channel (0.5 ms of a 6.5 M-point map's 0.57 ms).  A stale read only costs a needless atomic: the
+    // words move one way.
+    __shared__ uint32_t part[4][6];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {  // (every lane is here: the DPP reductions need the whole wave)
+        const float l = wave_minf(lo[k]), h = wave_maxf(hi[k]);
+        if ((threadIdx.x & 63) == 0) {
+            part[threadIdx.x >> 6][k] = float_ord(l);
+            part[threadIdx.x >> 6][3 + k] = float_ord(h);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 6) {
+        const int k = threadIdx.x;
+        uint32_t v = part[0][k];
+        for (int w = 1; w < 4; ++w) v = k < 3 ? min(v, part[w][k]) : max(v, part[w][k]);
+        const uint32_t cur = __builtin_nontemporal_load(&bbox[k]);
+        if (k < 3 ? v < cur : v > cur) {
+            if (k < 3) atomicMin(&bbox[k], v);
+            else atomicMax(&bbox[k], v);
+        }
+    }
+}
+
+hipError_t launch_finite_bbox(const float4* pts, int64_t n, uint32_t* bbox, hipStream_t st) {
+    hipError_t e;
+    if ((e = hipMemsetAsync(bbox, 0xFF, 3 * sizeof(uint32_t), st)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(bbox + 3, 0, 3 * sizeof(uint32_t), st)) != hipSuccess) return e;
+    const int64_t bb = (n + 255) / 256;
+    if (bb > 0) hipLaunchKernelGGL(finite_bbox_kernel,dim3((unsigned)(bb < 2048 ? bb : 2048)), dim3(256), 0, st, pts, n, bbox);
+    return hipGetLastError();
 }
 
 // KD_TREE::same_point (ikd_Tree.cpp:1422-1423): float fabs against the double 1e-6.

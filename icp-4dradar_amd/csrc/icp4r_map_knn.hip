@@ -25,42 +25,6 @@ constexpr int kKnnTile = 1024;          // points per LDS tile of the sweep
 constexpr uint32_t kKnnKeyBits = 31;    // 30 Morton bits; bit 30: a non-finite point, sorted last
 static_assert(kKnnLeaf % kKnnL == 0 && kKnnFan == 64, "a node's children are one wave's lanes");
 
-__device__ __forceinline__ bool knn_finite(const float4 p) {
-    return fabsf(p.x) < INFINITY && fabsf(p.y) < INFINITY && fabsf(p.z) < INFINITY;  // false for NaN
-}
-
-// float <-> uint32 with the floats' order, for integer atomicMin / atomicMax
-__device__ __forceinline__ uint32_t knn_ord(float f) {
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float knn_unord(uint32_t u) {
-    return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
-}
-
-// bbox[0..2] = min, bbox[3..5] = max over the finite points (set to all-ones / zero beforehand; no
-// finite point leaves min = +inf, max = -inf).
-__global__ __launch_bounds__(256) void knn_bbox_kernel(const float4* __restrict__ pts, int64_t n,
-                                                       uint32_t* __restrict__ bbox) {
-    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const float4 p = pts[i];
-        if (knn_finite(p)) {
-            lo[0] = fminf(lo[0], p.x), hi[0] = fmaxf(hi[0], p.x);
-            lo[1] = fminf(lo[1], p.y), hi[1] = fmaxf(hi[1], p.y);
-            lo[2] = fminf(lo[2], p.z), hi[2] = fmaxf(hi[2], p.z);
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {  // (every lane is here: the DPP reductions need the whole wave)
-        const float l = wave_minf(lo[k]), h = wave_maxf(hi[k]);
-        if ((threadIdx.x & 63) == 0) {
-            atomicMin(&bbox[k], knn_ord(l));
-            atomicMax(&bbox[3 + k], knn_ord(h));
-        }
-    }
-}
-
 // The key grid of a bounding box: 2047 / 2047 / 255 cells along x / y / z; a zero, infinite or
 // undefined extent gives scale 0, so every point of a flat, single-point or empty cloud has cell 0.
 struct KnnGrid {
@@ -70,8 +34,8 @@ __device__ __forceinline__ KnnGrid knn_grid(const uint32_t* __restrict__ bbox) {
     KnnGrid g;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        g.lo[k] = knn_unord(bbox[k]);
-        const float ext = knn_unord(bbox[3 + k]) - g.lo[k];
+        g.lo[k] = float_unord(bbox[k]);
+        const float ext = float_unord(bbox[3 + k]) - g.lo[k];
         g.sc[k] = (ext > 0.0f && ext < INFINITY) ? (k == 2 ? 255.0f : 2047.0f) / ext : 0.0f;
     }
     return g;
@@ -105,7 +69,7 @@ __global__ __launch_bounds__(256) void knn_keys_kernel(const float4* __restrict_
     if (i >= n) return;
     const KnnGrid g = knn_grid(bbox);
     const float4 p = pts[i];
-    pairs[i] = make_int2(knn_finite(p) ? (int32_t)knn_morton(p, g) : (int32_t)(1u << 30), (int32_t)i);
+    pairs[i] = make_int2(finite_xyz(p) ? (int32_t)knn_morton(p, g) : (int32_t)(1u << 30), (int32_t)i);
 }
 
 // The copy in key order, a whole number of leaves long: a non-finite point and the padding hold NaN
@@ -119,7 +83,7 @@ __global__ __launch_bounds__(256) void knn_gather_kernel(const float4* __restric
     if (t < n) {
         const int32_t i = pairs[t].y;
         const float4 p = pts[i];
-        if (knn_finite(p)) v = p;
+        if (finite_xyz(p)) v = p;
         v.w = __uint_as_float((uint32_t)i);
     }
     sorted[t] = v;
@@ -230,10 +194,7 @@ hipError_t launch_knn_index(const float4* pts, int64_t n, void* index, void* scr
     uint32_t* bbox = reinterpret_cast<uint32_t*>(w + L.bbox);
     float4* sorted = reinterpret_cast<float4*>(w + L.sorted);
     hipError_t e;
-    if ((e = hipMemsetAsync(bbox, 0xFF, 3 * sizeof(uint32_t), st)) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(bbox + 3, 0, 3 * sizeof(uint32_t), st)) != hipSuccess) return e;
-    const int64_t bb = (n + 255) / 256;
-    hipLaunchKernelGGL(knn_bbox_kernel, dim3((unsigned)(bb < 2048 ? bb : 2048)), dim3(256), 0, st, pts, n, bbox);
+    if ((e = launch_finite_bbox(pts, n, bbox, st)) != hipSuccess) return e;
     const int2* pairs = knn_sorted_pairs(pts, (int32_t)n, bbox, scratch, st);
     const int32_t npad = L.cnt[0] * kKnnLeaf;
     const unsigned gp = (unsigned)(((int64_t)npad + 255) / 256);
@@ -338,7 +299,7 @@ __global__ __launch_bounds__(kKnnWG) void map_knn_kernel(const KnnSearch a, cons
         o = order ? order[slot].y : (int32_t)slot;
         qv = a.q[o];
     }
-    const bool ok = have && knn_finite(qv);  // a query with a non-finite coordinate finds nothing
+    const bool ok = have && finite_xyz(qv);  // a query with a non-finite coordinate finds nothing
     KnnLane<K> q;
     // empty slots hold (+inf, ~0): a real d² bound for the pruning tests, told from a stored point at
     // distance +inf by the index
@@ -373,7 +334,7 @@ __global__ __launch_bounds__(kKnnWG) void map_knn_kernel(const KnnSearch a, cons
         __syncthreads();
         for (int t = sub; t < len; t += L) {
             const float4 v = tile[t];
-            q.consider(v.x, v.y, v.z, (uint32_t)(j0 + t), knn_finite(v));
+            q.consider(v.x, v.y, v.z, (uint32_t)(j0 + t), finite_xyz(v));
         }
     }
 

@@ -82,6 +82,11 @@ MAP_EXPORTED_SYMBOLS = [
 MAP_KNN_EXPORTED_SYMBOLS = [
     "icp4r_map_nearest_search", "icp4r_map_nearest_search_device", "icp4r_map_index_build", "icp4r_map_index_stats",
 ]
+# include/icp4r/icp4r_voxel.h (voxel-grid downsampling, pcl::VoxelGrid; icp4r.voxel)
+VOXEL_EXPORTED_SYMBOLS = [
+    "icp4r_voxel_params_default", "icp4r_voxel_filter", "icp4r_voxel_filter_device", "icp4r_map_voxel_filter",
+    "icp4r_map_voxel_filter_device", "icp4r_voxel_time_ms", "icp4r_voxel_time_reset",
+]
 
 
 def status_name(code: int) -> str:
@@ -216,6 +221,14 @@ def load():
         "icp4r_map_nearest_search_device": (C.c_int, [vp, vp, i64, i32, C.c_double, i32, vp, vp, vp, vp, vp]),
         "icp4r_map_index_build": (C.c_int, [vp]),
         "icp4r_map_index_stats": (C.c_int, [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i32)]),
+        # icp4r_voxel.h (the params struct: icp4r.voxel.VoxelParams)
+        "icp4r_voxel_params_default": (C.c_int, [vp]),
+        "icp4r_voxel_filter": (C.c_int, [vp, vp, i64, i32, vp, vp, i64, C.POINTER(i64)]),
+        "icp4r_voxel_filter_device": (C.c_int, [vp, vp, i64, vp, vp, vp, vp]),
+        "icp4r_map_voxel_filter": (C.c_int, [vp, vp, vp, i64, C.POINTER(i64)]),
+        "icp4r_map_voxel_filter_device": (C.c_int, [vp, vp, vp, vp, vp]),
+        "icp4r_voxel_time_ms": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(i32)]),
+        "icp4r_voxel_time_reset": (C.c_int, [vp]),
         # icp4r_multi.h
         "icp4r_shard": (C.c_int, [i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]),
         "icp4r_align_batch_multi": (C.c_int, [C.POINTER(vp), i32, vp, vp, vp, vp, vp, vp, i32, vp, C.POINTER(Params),

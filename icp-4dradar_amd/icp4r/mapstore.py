@@ -21,6 +21,7 @@ import ctypes as C
 import numpy as np
 
 from . import E_INVALID, Context, ICP4RError, _check, _cloud, _ptr, default_context, load
+from .voxel import voxel_params
 
 RADAR_RADIUS = 80.0  # radar_odometry.cpp:36
 KNN_MAX_K = 32  # ICP4R_MAP_KNN_MAX_K
@@ -146,6 +147,17 @@ class KD_TREE:  # noqa: N801 — the reference's class name
                                                   _ptr(idx), _ptr(found)), "icp4r_map_nearest_search")
         return pts, dist, idx, found
 
+    def voxel_filter(self, leaf, downsample_all_data: bool = True, min_points_per_voxel: int = 0) -> np.ndarray:
+        """pcl::VoxelGrid over the stored points (the node's surround map, radar_odometry.cpp:426-429;
+        include/icp4r/icp4r_voxel.h): (K, 4) float32 centroids in ascending leaf index.  leaf: one float
+        or three.  The store and its k-NN index are left as they are."""
+        p = voxel_params(leaf, downsample_all_data, min_points_per_voxel)
+        cap = self.size()
+        out = np.empty((max(cap, 1), 4), np.float32)
+        k = C.c_int64()
+        _check(self._lib.icp4r_map_voxel_filter(self._h, C.byref(p), _ptr(out), cap, C.byref(k)), "icp4r_map_voxel_filter")
+        return out[:k.value].copy()
+
     def index_build(self):
         """Brings the k-NN index up to date now (a search does so by itself when it has to)."""
         _check(self._lib.icp4r_map_index_build(self._h), "icp4r_map_index_build")
@@ -202,6 +214,15 @@ class KD_TREE:  # noqa: N801 — the reference's class name
         _check(self._lib.icp4r_map_nearest_search_device(self._h, vp(d_queries), nq, int(k), float(max_dist), int(flags),
                                                          vp(d_points), vp(d_dist), vp(d_index), vp(d_found),
                                                          vp(stream)), "icp4r_map_nearest_search_device")
+
+    def voxel_filter_device(self, leaf, d_out: int, d_count: int, downsample_all_data: bool = True,
+                            min_points_per_voxel: int = 0, stream=None):
+        """The store's voxel centroids (float4, room for size() points) to device address d_out and their
+        int32 count to d_count (-1: grid overflow); nothing leaves the device and the store is unchanged."""
+        p = voxel_params(leaf, downsample_all_data, min_points_per_voxel)
+        _check(self._lib.icp4r_map_voxel_filter_device(self._h, C.byref(p), C.c_void_p(d_out), C.c_void_p(d_count),
+                                                       C.c_void_p(stream) if stream else None),
+               "icp4r_map_voxel_filter_device")
 
     def points_device(self) -> tuple[int, int]:
         p, n = C.c_void_p(), C.c_int64()
