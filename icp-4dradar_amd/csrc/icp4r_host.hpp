@@ -141,4 +141,7 @@ struct icp4r_ctx {
     icp4r_host::DevBuf vox_work, vox_in, vox_out, vox_cnt;
     std::vector<icp4r_host::EventPair> vox_events;
     size_t vox_used = 0;
+    // the Doppler gate (icp4r_gate.cpp): the compaction's workspace (tile counts and bases), the guarded
+    // counts and flags, the mask when the caller keeps none, the host entries' packed clouds and descriptors
+    icp4r_host::DevBuf gate_counts, gate_base, gate_cnt, gate_bad, gate_mask, gate_clouds, gate_pair_off, gate_pair_n;
 };

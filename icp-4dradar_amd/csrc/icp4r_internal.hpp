@@ -429,6 +429,30 @@ struct EgoArgs {
 hipError_t launch_ego(const EgoArgs& e, int nscans, int max_n, float4* xyzi, hipStream_t st);
 hipError_t launch_ego_features(const EgoArgs& e, int nscans, int max_n, float4* xyzi, hipStream_t st);
 
+// ---- the Doppler gate (icp4r_gate.hip; include/icp4r/icp4r_gate.h)
+constexpr int kGateTile = 1024;  // points per (scan, tile) of the compaction: one wave, 16 mask bytes a lane
+struct GateArgs {
+    const float4* xyzi;    // device points, point i of scan s at off[s] + i
+    const int64_t* off;    // [nscans]
+    const int32_t* cnt;    // [nscans]; a count < 0 or > max_n packs nothing
+    const uint8_t* mask;   // one byte per point, indexed like xyzi (unused when all != 0)
+    int32_t nscans, max_n;
+    int32_t tiles;         // tiles per scan: ceil(max_n / kGateTile), at least 1
+    int32_t all;           // ICP4R_GATE_ALL: keep every point
+    int32_t* counts;       // workspace [nscans * tiles]: kept points per tile
+    int64_t* base;         // workspace [nscans * tiles]: first packed index per tile
+    float4* clouds;        // out: the packed points
+    int64_t* pair_off;     // out [nscans + 1]: [s0, s0, s1, ...]
+    int32_t* pair_n;       // out [nscans + 1]
+    const int32_t* bad;    // optional [nscans] (launch_gate_guard): results[s].status := ICP4R_E_INVALID where set
+    icp4r_ego_result* results;
+};
+hipError_t launch_gate(const GateArgs& g, hipStream_t st);
+// cnt_safe[s] = cnt[s] where the ego kernels stay inside a workspace of cap records (off[s] >= 0 and
+// off[s] + min(cnt[s], max_n) <= cap), else 0 with bad[s] = 1
+hipError_t launch_gate_guard(const int64_t* off, const int32_t* cnt, int nscans, int max_n, int64_t cap, int32_t* cnt_safe,
+                             int32_t* bad, hipStream_t st);
+
 // ---- generalized ICP (icp4r_gicp.hip): fast_gicp's LsqRegistration state per pair
 struct GicpState {
     double R[9], t[3];  // x0 (row-major rotation, translation)

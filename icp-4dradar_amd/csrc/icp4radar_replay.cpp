@@ -14,11 +14,20 @@
 // velocity of the current scan (icp4r_ego_velocity: fitSineRansac + split + LSQ, :387-431), ICP of
 // curr against last with PCL defaults through the pcl::IterativeClosestPoint facade (:505-521), pose
 // composition currOdom = currOdom * T, t += Rtrans * dt, Rtrans = Rtrans * dR (:541-556).  ROS topics,
-// the 20-frame submap publisher (:577-633) and stdout are not reproduced; the node's RANSAC of the
-// previous scan (:465-493) feeds nothing that is written and is skipped.
+// the 20-frame submap publisher (:577-633) and stdout are not reproduced.  Without --static-points the
+// node's RANSAC of the previous scan (:465-493) feeds nothing that is written and is skipped.
 //
 //   icp4radar_replay <dataset_folder> [--csv PATH] [--batch] [--devices D0,D1,...] [--seed S]
-//                    [--max-iterations N] [--use-icp-result CSV]
+//                    [--max-iterations N] [--use-icp-result CSV] [--static-points]
+//
+// --static-points: the node built with USE_STATIC_POINTS — only the static points of a scan (delta <=
+// 0.2 against its own sine model, :391-407) are pushed onto cloud_src_in / cloud_tar_in (:404-406,
+// :482-484), so ICP runs on the Doppler-gated clouds and the running-cloud rule below sees the static
+// counts.  pcl_info.txt still prints the raw point count (:325).  Each scan is split once, with its own
+// seed, and that split serves it as source and as target (the node re-runs fitSineRansac on the previous
+// scan from a fresh std::random_device, :467; include/icp4r/icp4r_gate.h).  Per frame: icp4r_static_cloud
+// and the facade; with --batch: ONE call, icp4r_register_static_sequence (ICP4R_PAIR_NODE) — upload, ego
+// velocity, gate, pairing and the batched ICP with one read-back of the counts.  Byte-identical outputs.
 //
 // Empty scans (:505 vs :698-699): the node pushes every frame's points onto cloud_src_in /
 // cloud_tar_in and clears them only inside `if (cloud_tar_in->size() && cloud_src_in->size())`.
@@ -61,6 +70,7 @@
 
 #include "icp4r/icp4r.h"
 #include "icp4r/icp4r_ego.h"
+#include "icp4r/icp4r_gate.h"
 #include "icp4r/icp4r_multi.h"
 #include "icp4r/pcl_compat.hpp"
 
@@ -128,7 +138,7 @@ struct FrameOut {
 
 int usage() {
     std::fprintf(stderr, "usage: icp4radar_replay <dataset_folder> [--csv PATH] [--batch] [--devices D0,D1,...] [--seed S] "
-                         "[--max-iterations N] [--use-icp-result CSV]\n");
+                         "[--max-iterations N] [--use-icp-result CSV] [--static-points]\n");
     return 2;
 }
 
@@ -140,6 +150,7 @@ int main(int argc, char** argv) {
     if (dataset_folder.empty() || dataset_folder.back() != '/') dataset_folder += "/";
     std::string csv = dataset_folder + "output_result.csv";
     bool batch = false;
+    bool static_points = false;  // --static-points: the node's USE_STATIC_POINTS
     std::vector<int> devices;  // --devices: the batch sharded over these (icp4r_align_batch_multi)
     icp4r_ego_params ep;
     icp4r_ego_params_default(&ep);
@@ -160,9 +171,13 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--seed") && i + 1 < argc) ep.seed = std::strtoull(argv[++i], nullptr, 0);
         else if (!std::strcmp(argv[i], "--max-iterations") && i + 1 < argc) max_iterations = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--use-icp-result") && i + 1 < argc) icp_result_csv = argv[++i];
+        else if (!std::strcmp(argv[i], "--static-points")) static_points = true;
         else return usage();
     }
     const bool use_icp_result = !icp_result_csv.empty();
+    if (static_points && !devices.empty()) return usage();  // the gated sequence runs on one context
+    // the gated sequence in one call: ego velocity, gate, pairing and ICP (below)
+    const bool one_call = static_points && batch && !use_icp_result;
     const std::string out_dir = dataset_folder + "radar";
     if (!exists(out_dir) && mkdir(out_dir.c_str(), 0755) != 0) {  // the node shells out to `sudo mkdir` (:151-156)
         std::perror("mkdir");
@@ -193,9 +208,12 @@ int main(int argc, char** argv) {
     icp4r_params_default(&ip);
     if (max_iterations >= 0) ip.max_iterations = max_iterations;
 
+    // --static-points: the points each scan pushes onto the running clouds (float4), else its records
+    std::vector<std::vector<float>> gated(static_points ? nframes : 0);
     for (size_t k = 0; k < nframes; ++k) {
         const std::vector<float>& curr = scans[k];
         pcl_info << curr.size() / 5.0 << std::endl;
+        if (one_call) continue;
         // radar ego velocity of the current scan (:352-431); frame k draws from seed + (k << 32)
         icp4r_ego_params pk = ep;
         pk.seed = ep.seed + ((uint64_t)k << 32);
@@ -205,9 +223,17 @@ int main(int argc, char** argv) {
             out[k].A = out[k].b = 0.0;
             continue;
         }
-        int rc = icp4r_ego_velocity(ctx, curr.data(), n, &pk, &er, nullptr, nullptr);
+        int rc;
+        if (static_points) {  // the ego velocity and the static points (:391-407) in one call
+            int32_t n_static = 0;
+            gated[k].resize((size_t)n * 4);
+            rc = icp4r_static_cloud(ctx, curr.data(), n, &pk, &er, gated[k].data(), &n_static);
+            gated[k].resize((size_t)(rc == ICP4R_OK ? n_static : 0) * 4);
+        } else {
+            rc = icp4r_ego_velocity(ctx, curr.data(), n, &pk, &er, nullptr, nullptr);
+        }
         if (rc != ICP4R_OK && rc != ICP4R_E_EMPTY) {
-            std::fprintf(stderr, "icp4r_ego_velocity: %s\n", icp4r_last_error());
+            std::fprintf(stderr, "%s: %s\n", static_points ? "icp4r_static_cloud" : "icp4r_ego_velocity", icp4r_last_error());
             return 1;
         }
         out[k].A = er.A;
@@ -223,15 +249,20 @@ int main(int argc, char** argv) {
         std::vector<float> src, tgt;  // float4 x, y, z, intensity
     };
     std::vector<PairIn> pairs;
-    {
+    if (!one_call) {
         std::vector<float> acc_src, acc_tgt;
-        auto push = [](std::vector<float>& acc, const std::vector<float>& rec) {
+        auto push = [&](std::vector<float>& acc, size_t scan) {
+            if (static_points) {  // the scan's static points, already float4
+                acc.insert(acc.end(), gated[scan].begin(), gated[scan].end());
+                return;
+            }
+            const std::vector<float>& rec = scans[scan];
             const size_t n = rec.size() / 5;
             for (size_t i = 0; i < n; ++i) acc.insert(acc.end(), &rec[5 * i], &rec[5 * i] + 4);
         };
         for (size_t k = 0; k < nframes; ++k) {
-            push(acc_src, scans[k]);
-            push(acc_tgt, scans[k ? k - 1 : 0]);
+            push(acc_src, k);
+            push(acc_tgt, k ? k - 1 : 0);
             if (acc_src.empty() || acc_tgt.empty()) continue;  // not registered, not cleared
             pairs.push_back({k, std::move(acc_src), std::move(acc_tgt)});
             acc_src.clear();
@@ -239,7 +270,39 @@ int main(int argc, char** argv) {
         }
     }
 
-    if (use_icp_result) {
+    if (one_call) {
+        // USE_STATIC_POINTS, the whole sequence in one call (include/icp4r/icp4r_gate.h)
+        std::vector<float> records;
+        std::vector<int64_t> off(nframes);
+        std::vector<int32_t> cnt(nframes), registered(nframes);
+        for (size_t k = 0; k < nframes; ++k) {
+            off[k] = (int64_t)(records.size() / 5);
+            cnt[k] = (int32_t)(scans[k].size() / 5);
+            records.insert(records.end(), scans[k].begin(), scans[k].begin() + (size_t)cnt[k] * 5);
+        }
+        std::vector<icp4r_ego_result> er(nframes);
+        std::vector<icp4r_result> res(nframes);
+        int rc = icp4r_register_static_sequence(ctx, records.data(), off.data(), cnt.data(), (int32_t)nframes, &ep, &ip,
+                                                ICP4R_GATE_STATIC, ICP4R_PAIR_NODE, er.data(), res.data(),
+                                                registered.data());
+        if (rc != ICP4R_OK) {
+            std::fprintf(stderr, "icp4r_register_static_sequence: %s\n", icp4r_last_error());
+            return 1;
+        }
+        for (size_t k = 0; k < nframes; ++k) {
+            FrameOut& f = out[k];
+            if (cnt[k] > 0) {  // (an empty scan: A = b = 0, Vxyz = 0, as in the loop above)
+                f.A = er[k].A;
+                f.b = er[k].b;
+                for (int c = 0; c < 3; ++c) f.V[c] = er[k].v[c];
+            }
+            if (!registered[k]) continue;
+            f.registered = true;
+            for (int r = 0; r < 4; ++r)
+                for (int c = 0; c < 4; ++c) f.T[4 * r + c] = (double)res[k].T[4 * c + r];  // column-major float
+            f.score = res[k].fitness;
+        }
+    } else if (use_icp_result) {
         // USE_ICP_RESULT (:192-206, :523-540): transforms from a previous run's CSV, no ICP
         std::ifstream file(icp_result_csv.c_str());
         if (!file) {

@@ -61,6 +61,11 @@ PLAN_OPTIONS = (
 EGO_EXPORTED_SYMBOLS = [
     "icp4r_ego_params_default", "icp4r_radar_features", "icp4r_ego_velocity", "icp4r_ego_velocity_batch_device",
 ]
+# include/icp4r/icp4r_gate.h (Doppler-gated registration: the static-point gate; icp4r.ego)
+GATE_EXPORTED_SYMBOLS = [
+    "icp4r_compact_by_mask_batch_device", "icp4r_static_clouds_batch_device", "icp4r_static_cloud",
+    "icp4r_sequence_pairs", "icp4r_register_static_sequence", "icp4r_register_static_sequence_ex",
+]
 # include/icp4r/icp4r_gicp.h (generalized ICP; icp4r.gicp)
 GICP_EXPORTED_SYMBOLS = [
     "icp4r_gicp_params_default", "icp4r_gicp_align", "icp4r_gicp_align_batch_device", "icp4r_gicp_covariances",

@@ -195,3 +195,61 @@ def read_bin(path: str | os.PathLike) -> np.ndarray:
 def records_to_xyzi(records: np.ndarray) -> np.ndarray:
     """The node's PointXYZI fill (``:404-406``): x, y, z, intensity; ``v_r`` is dropped."""
     return np.ascontiguousarray(records[:, :4], dtype=np.float32)
+
+
+def make_sequence_movers(index: int = 0, frames: int = 6, n: int = 2048, mover: float = 0.25,
+                         mover_velocity=(4.0, 3.0, 0.0), mover_start=(18.0, -3.0, 0.0), speed: float = 5.0,
+                         dt: float = 0.1, yaw_rate_deg: float = 2.0, el_deg: float = 3.0,
+                         doppler_noise: float = 0.02, pool: float = 1.25) -> tuple[list[np.ndarray], np.ndarray, list[np.ndarray]]:
+    """``make_sequence`` with one coherent moving object instead of scattered dynamic points (seed
+    ``9500 + index``): a ``mover`` fraction of every scan lies on a rigid object — the rear face
+    (8 m x 2.5 m) and one side (6 m) of a vehicle — that starts at ``mover_start`` and moves through the
+    world at ``mover_velocity`` m/s.  Its points carry the matching Doppler ``v_r = û·(v_object −
+    v_sensor)``; the others are the static scene with ``v_r = -û·v_sensor``.  Registered with every
+    point, the object drags the pose towards its own motion; the node's ``delta > 0.2`` test removes
+    it (it recedes, so its ``v_r`` lies above the static model).  Returns the per-frame (N, 5) records,
+    the sensor velocity in the sensor frame, and per frame k the true 4x4 transform of scan k into
+    the frame of scan k-1 (identity for k = 0): what ICP of frame k estimates."""
+    rng = np.random.default_rng(9500 + index)
+    n_obj = int(round(mover * n))
+    n_bg = n - n_obj
+    world = _sensor_points(rng, int(pool * n_bg) + 1, structured=True, el_deg=el_deg)
+    # the object's body: points on the rear face x = 0 and on the side y = 4, in its own frame
+    m = int(pool * n_obj) + 1
+    rear = np.stack([np.zeros(m), rng.uniform(-4.0, 4.0, m), rng.uniform(-0.6, 0.6, m)], axis=1)
+    side = np.stack([rng.uniform(0.0, 6.0, m), np.full(m, 4.0), rng.uniform(-0.6, 0.6, m)], axis=1)
+    body = np.where((rng.random(m) < 0.6)[:, None], rear, side)
+    v_sensor = np.array([speed, 0.0, 0.0])
+    w = np.asarray(mover_velocity, np.float64)
+    c = np.asarray(mover_start, np.float64).copy()
+    t = np.zeros(3)
+    yaw = 0.0
+    out, truth = [], []
+    R_prev, t_prev = np.eye(3), np.zeros(3)
+    for k in range(frames):
+        R = _rot_zyx(yaw, 0.0, 0.0)
+        sel = rng.choice(len(world), size=n_bg, replace=False)
+        osel = rng.choice(len(body), size=n_obj, replace=False)
+        pw = np.concatenate([world[sel], body[osel] + c])
+        is_obj = np.concatenate([np.zeros(n_bg, bool), np.ones(n_obj, bool)])
+        order = rng.permutation(n)  # the object's points are spread through the scan
+        pw, is_obj = pw[order], is_obj[order]
+        p = (pw - t) @ R + rng.normal(0.0, 0.02, (n, 3))  # R^T (p - t), row form
+        u = p / np.linalg.norm(p, axis=1, keepdims=True)
+        vr = -(u @ v_sensor) + rng.normal(0.0, doppler_noise, n)
+        vr[is_obj] += u[is_obj] @ (R.T @ w)
+        rec = np.empty((n, RECORD_FLOATS), np.float32)
+        rec[:, :3] = p
+        rec[:, 3] = rng.uniform(0.0, 30.0, n)
+        rec[:, 4] = vr
+        out.append(rec)
+        T = np.eye(4)
+        if k:
+            T[:3, :3] = R_prev.T @ R
+            T[:3, 3] = R_prev.T @ (t - t_prev)
+        truth.append(T)
+        R_prev, t_prev = R, t
+        t = t + R @ v_sensor * dt
+        c = c + w * dt
+        yaw += np.deg2rad(yaw_rate_deg) * dt
+    return out, v_sensor, truth
