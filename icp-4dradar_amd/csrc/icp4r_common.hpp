@@ -1,6 +1,6 @@
 // icp4r_common.hpp — the base of the ICP kernel units' include chain: the includes they all need, the
-// ICP4R_WG_TICKS default, and what the index build (icp4r_index.hip) shares with the search and update kernels
-// (icp4r_kernels.hip): the sizes of the two orders, the Morton cell code and its quantisation, and the packing
+// ICP4R_WG_TICKS default, and what the index build (icp4r_index.hip) shares with the other stages
+// (icp4r_kernels.hip, icp4r_frame.hip): the sizes of the two orders, the Morton cell code and its quantisation, and the packing
 // of a query's index and sorted position.  No kernel.
 #pragma once
 

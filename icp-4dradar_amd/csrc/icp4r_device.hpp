@@ -1,5 +1,5 @@
 // icp4r_device.hpp — device-side helpers shared by the kernel translation units
-// (icp4r_index.hip, icp4r_kernels.hip, icp4r_gicp.hip, icp4r_map.hip, icp4r_map_knn.hip): scalar-cache pointers,
+// (icp4r_index.hip, icp4r_kernels.hip, icp4r_frame.hip, icp4r_gicp.hip, icp4r_map.hip, icp4r_map_knn.hip): scalar-cache pointers,
 // the XCD-aware work mapping, the slotted work counters, the NN key, the top-K lists and the map's distance.
 #pragma once
 

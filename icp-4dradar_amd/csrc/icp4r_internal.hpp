@@ -207,7 +207,8 @@ constexpr int kMaxTickPasses = 64;  // passes with their own slots (later passes
 // first per-pass slot of a batch of npairs (after the pair-0 stamps and the per-pair debug slots)
 inline int64_t pass_tick_base(int npairs) { return 32 + 20 * (int64_t)npairs; }
 
-// ---- the ICP path (launch_index, launch_index_cloud: icp4r_index.hip; the others: icp4r_kernels.hip).
+// ---- the ICP path (launch_index, launch_index_cloud: icp4r_index.hip; launch_init, launch_fitness_prep,
+// launch_finish, launch_rot_f32: icp4r_frame.hip; the others: icp4r_kernels.hip).
 // One registration = SURVEY.md §3.2 / Appendix A.  It runs on the
 // device as a fixed sequence of launches with no host synchronisation: per-pair phase flags (PairState)
 // let a finished pair's workgroups return at once.  run_pairs (icp4r_capi.cpp) picks one of:

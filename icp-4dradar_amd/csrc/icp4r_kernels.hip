@@ -1,7 +1,7 @@
-// icp4r_kernels.hip — the ICP kernels other than the index build (icp4r_index.hip): init, the NN searches,
-// the updates, solo_kernel, the fitness pass and finish, with their launches.  The launch sequences are
-// written out above the launch_* declarations in icp4r_internal.hpp.
-#include "icp4r_common.hpp"
+// icp4r_kernels.hip — the NN searches, the updates and solo_kernel, with their launches (the index build:
+// icp4r_index.hip; init, the fitness prep and finish: icp4r_frame.hip).  The launch sequences are written out above
+// the launch_* declarations in icp4r_internal.hpp.
+#include "icp4r_fold.hpp"
 
 namespace icp4r {
 
@@ -90,13 +90,6 @@ __device__ __forceinline__ void nn_sweep_packed(const float (&x)[Q], const float
     }
 }
 
-template <typename T>
-__device__ __forceinline__ T wave_sum(T v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 // Sum N doubles over a workgroup of NW waves in a fixed order (xor-butterfly per wave, then waves
 // in index order by thread k for component k); totals land in `out` (LDS).
 template <int N, int NW>
@@ -117,151 +110,12 @@ __device__ __forceinline__ void block_sum(double (&v)[N], double* sh /* [NW*N] *
     __syncthreads();
 }
 
-__device__ __forceinline__ double huber_w(float d2, double delta) {
-    const double r = sqrt((double)d2);
-    return r <= delta ? 1.0 : delta / r;
-}
-
 // Per-query NN result: one key (splits were merged by atomicMin on the key, i.e. the lexicographic
 // (d², index) minimum == the unsplit sweep's answer).
 __device__ __forceinline__ void load_nn(const WorkArgs& w, int64_t slot, float& d2, int& idx) {
     const NNKey k = w.nn_key[slot];
     d2 = key_d2(k);
     idx = key_idx(k);
-}
-
-// Correspondence records (PCL numerics): per source point, in source-index order (the fold order),
-// two float4 at corr + (p*x_stride + i)*2: {s.xyz (the transformed source point searched with),
-// w (Huber weight, 1 unweighted)}, {d.xyz (its nearest target), d² (float, as FLANN returned it)}.
-// Written by the pruned NN kernel's tail, or by corr_kernel after a brute-force pass.
-__device__ __forceinline__ void write_corr(const WorkArgs& w, const PairArgs& a, int p, int i, float sx, float sy,
-                                           float sz, NNKey k, const float4* tgt) {
-    float4* C = w.corr + ((int64_t)p * w.x_stride + i) * 2;
-    const float d2 = key_d2(k);
-    const float4 t = tgt[key_idx(k)];
-    const float wt = a.kp.huber_delta < INFINITY ? (float)huber_w(d2, a.kp.huber_delta) : 1.0f;
-    C[0] = make_float4(sx, sy, sz, wt);
-    C[1] = make_float4(t.x, t.y, t.z, d2);
-}
-
-// ---------------------------------------------------------------------------------------------
-// init_kernel: one workgroup per pair.
-// WG threads per pair: 256 for batches (HBM-bound there), 1024 for a few pairs, whose validation
-// passes are latency-bound rounds of loads (C5's 65k-point map: 16 rounds of 256 x 16 -> 4)
-template <int kInitWG>
-__global__ __launch_bounds__(kInitWG) void init_kernel(PairArgs a, WorkArgs w) {
-    __shared__ float Tg[16];
-    __shared__ int ident;
-    const int p = xcd_remap(blockIdx.x, gridDim.x);
-    const int tid = threadIdx.x;
-    const int n = a.src_n[p], m = a.tgt_n[p];
-    const float4* src = a.src + a.src_off[p];
-    const float4* tgt = a.tgt + a.tgt_off[p];
-    PairState& st = w.state[p];
-    if (tid < 16) Tg[tid] = a.guess ? a.guess[(int64_t)p * 16 + tid] : ((tid % 5 == 0) ? 1.0f : 0.0f);
-    __syncthreads();
-    if (tid == 0) {
-        bool id = true;
-        for (int k = 0; k < 16; ++k) id = id && (Tg[k] == ((k % 5 == 0) ? 1.0f : 0.0f));
-        ident = id ? 1 : 0;
-    }
-    __syncthreads();
-    // One pass over the source: validated and written transformed (transformCloud(input, guess)) in
-    // the same read — X of a pair found invalid below is never read.  Counts above the workspace
-    // stride are not copied (too_big below marks the pair invalid).  kInitPer points per thread in
-    // flight, every load of a round before its stores.
-    constexpr int kInitPer = 4;
-    float4* X = w.X + (int64_t)p * w.x_stride;
-    const bool id = ident != 0;
-    const int nc = min(n, (int)w.x_stride);
-    int bad = 0;
-    // coordinates beyond 1e17 could square into an overflowing (inf) distance, which PCL rejects: such
-    // a pair never skips pass A's distance check (PairState::sums_ok = -1)
-    constexpr float kBig = 1e17f;
-    int big = 0;
-    // (the target is only validated: 16 points per thread in flight — a scan-to-map target of 65k
-    // points had taken 64 dependent rounds of 1024, ~65 us of a single registration)
-    // (and its bounding box, for the Morton index of a large target: w.tbb)
-    constexpr int kTgtPer = 16;
-    float bl[3] = {INFINITY, INFINITY, INFINITY}, bh[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int i0 = 0; i0 < m; i0 += kInitWG * kTgtPer) {
-        float4 t[kTgtPer];
-#pragma unroll
-        for (int e = 0; e < kTgtPer; ++e) t[e] = tgt[min(i0 + e * kInitWG + tid, m - 1)];
-#pragma unroll
-        for (int e = 0; e < kTgtPer; ++e) {  // (a clamped duplicate of point m - 1 changes no extent)
-            bad |= !(isfinite(t[e].x) && isfinite(t[e].y) && isfinite(t[e].z));
-            big |= fmaxf(fabsf(t[e].x), fmaxf(fabsf(t[e].y), fabsf(t[e].z))) > kBig;
-            bl[0] = fminf(bl[0], t[e].x); bl[1] = fminf(bl[1], t[e].y); bl[2] = fminf(bl[2], t[e].z);
-            bh[0] = fmaxf(bh[0], t[e].x); bh[1] = fmaxf(bh[1], t[e].y); bh[2] = fmaxf(bh[2], t[e].z);
-        }
-    }
-    if (w.tbb) {
-        __shared__ float bred[kInitWG / 64][6];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {  // (DPP)
-            bl[k] = wave_minf(bl[k]);
-            bh[k] = wave_maxf(bh[k]);
-        }
-        if ((tid & 63) == 0)
-            for (int k = 0; k < 3; ++k) {
-                bred[tid >> 6][k] = bl[k];
-                bred[tid >> 6][3 + k] = bh[k];
-            }
-        __syncthreads();
-        if (tid < 6) {
-            float v = bred[0][tid];
-            for (int q = 1; q < kInitWG / 64; ++q) v = tid < 3 ? fminf(v, bred[q][tid]) : fmaxf(v, bred[q][tid]);
-            w.tbb[(int64_t)p * 8 + tid] = v;
-        }
-    }
-    for (int i0 = 0; i0 < n; i0 += kInitWG * kInitPer) {
-        float4 v[kInitPer];
-#pragma unroll
-        for (int e = 0; e < kInitPer; ++e) v[e] = src[min(i0 + e * kInitWG + tid, n - 1)];
-#pragma unroll
-        for (int e = 0; e < kInitPer; ++e) {
-            const int i = i0 + e * kInitWG + tid;
-            bad |= !(isfinite(v[e].x) && isfinite(v[e].y) && isfinite(v[e].z));
-            float4 o = v[e];
-            if (!id) xform_pt(Tg, v[e].x, v[e].y, v[e].z, o.x, o.y, o.z);
-            big |= fmaxf(fabsf(o.x), fmaxf(fabsf(o.y), fabsf(o.z))) > kBig;
-            if (i < nc) X[i] = o;
-        }
-    }
-    // the pass-scoped state this registration starts from: the pair's miss bitmap and count (cached-
-    // neighbour plans) and, by the group's first pair, its work-list counters (plist_n[0..3]: items,
-    // queue, part size, the fused order's arrival counter)
-    if (w.need) {
-        uint32_t* gneed = w.need + (int64_t)p * w.need_stride;
-        for (int k = tid; k < w.need_stride; k += kInitWG) gneed[k] = 0u;
-    }
-    if (tid == 0 && w.miss_cnt) w.miss_cnt[p] = 0;
-    if (tid < 4 && p == 0 && w.plist_n) w.plist_n[tid] = 0;
-    bad = __syncthreads_or(bad);
-    big = __syncthreads_or(big);
-    if (tid == 0) {
-        mat4_identity(st.T_inc);
-        st.prev_mse = DBL_MAX;
-        st.similar = 0;
-        st.conv_state = 0;
-        st.iterations = 0;
-        st.ncorr = 0;
-        st.sums_ok = big ? -1 : 0;
-        st.pending = 0;
-        // counts above the batch's declared max_src_n / max_tgt_n would overrun the workspace strides
-        const bool too_big = n > w.x_stride || (w.leaf > 0 && m > w.t_stride);
-        if (m <= 0 || bad || too_big) {
-            // Registration::initCompute fails (no target) -> align returns; final stays identity.
-            mat4_identity(st.final_T);
-            st.phase = kPhaseInvalid;
-            st.status = too_big ? kStatusInvalid : m <= 0 ? kStatusEmpty : kStatusNonFinite;
-        } else {
-            for (int k = 0; k < 16; ++k) st.final_T[k] = Tg[k];  // final_transformation_ = guess
-            st.phase = kPhaseActive;
-            st.status = 0;
-        }
-    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -580,12 +434,6 @@ constexpr int kLdsWG = 1024;
 constexpr int kLdsWaves = kLdsWG / 64;
 constexpr int kLdsQ = 1;  // queries per lane (2 measured no faster: smaller runs prune better)
 constexpr int kRing = 128;  // work items per wave (<= 63 pending + 64 appended per query slot)
-constexpr float kCacheMargin = 1.0e-4f;
-constexpr int kNeedWords = kCacheMaxN / 32;  // bitmap words per pair (one bit per Morton position)
-// miss_cnt[p]: the pass' misses, | kMissUnranked when the test left them unplaced (the pair's miss list
-// sq / sm and bitmap, for the search to place) instead of in rank order in qv / qm
-constexpr int32_t kMissUnranked = 1 << 30;
-constexpr int32_t kMissCount = kMissUnranked - 1;
 static_assert(kNeedWords <= kLdsWG, "compaction: one bitmap word per thread");
 
 // An LDS address held in a VGPR: a wave-uniform LDS address otherwise sits in an SGPR and every
@@ -676,22 +524,16 @@ struct LdsNN {
     int32_t nx[2][5];                                  // (claim-ahead) item k's {index, item, n, m, misses} in nx[k & 1]
 };
 
-
 // LDS slot of sorted target position p: the slot inside its 16-target block XOR the block's low
 // bits — an involution per block (bank spreading for the drain, see nn_lds_kernel)
 __device__ __forceinline__ int lds_swz(int p) { return p ^ ((p >> 4) & (kLdsLeaf - 1)); }
 
-// nn_t[i].w packs the NN's sorted target position (bits 0..13) and the query's sorted source position
-// (bits 14..27): the test reads one record for the miss bitmap's bit and for the search record it
-// writes (sq / sm: the next search's seed is that target position, no index lookup).  Sizes:
-// <= kCacheMaxN = 2^14 sources, <= 8192 targets on the batched plan.
+// (nn_t[i].w and the query records: nt_tpos / nt_pos, icp4r_nn.hpp)
 static_assert(kCacheMaxN <= (1 << kNtPosShift) && kLdsTargets <= (1 << kNtPosShift) && kLdsMaxSources == (1 << kNtPosShift),
               "nn_t.w / query record packing");
 __device__ __forceinline__ float nt_pack(int tpos, int pos) {
     return __uint_as_float((uint32_t)tpos | ((uint32_t)pos << kNtPosShift));
 }
-__device__ __forceinline__ uint32_t nt_tpos(float w) { return __float_as_uint(w) & kNtIdxMask; }
-__device__ __forceinline__ uint32_t nt_pos(float w) { return __float_as_uint(w) >> kNtPosShift; }
 
 // LDS target record .w during the batched search: original index << 13 | sorted position.  Keys
 // compare (d², original index) exactly as before (the index is unique and the position follows
@@ -700,59 +542,6 @@ constexpr int kLdsPosBits = 13;
 static_assert(kLdsTargets <= (1 << kLdsPosBits), "LDS key packing");
 __device__ __forceinline__ uint32_t lk_idx(NNKey k) { return (uint32_t)k >> kLdsPosBits; }
 __device__ __forceinline__ uint32_t lk_pos(NNKey k) { return (uint32_t)k & ((1u << kLdsPosBits) - 1); }
-
-// A missed query's search record, appended to its pair's miss list at slot k (in the order the
-// test found them): {X.xyz, U} and {its index | its NN's sorted target position << 14, its sorted
-// position}.  The search stages these by rank instead of gathering X, U and a seed per query.
-__device__ __forceinline__ void put_miss(const WorkArgs& w, int p, int k, uint32_t sp, int i, float x, float y,
-                                         float z, float U, uint32_t tpos) {
-    const int64_t slot = (int64_t)p * w.x_stride + k;
-    w.sq[slot] = make_float4(x, y, z, U);
-    // (one 8-B store: stored as two dwords, the second was merged with the LDS record's into a flat
-    // store that every miss of the fused test paid)
-    *reinterpret_cast<uint64_t*>(&w.sm[slot]) = (uint64_t)((uint32_t)i | (tpos << kNtPosShift)) | ((uint64_t)sp << 32);
-}
-
-// Slot of this lane's record in an append list shared by the workgroup (ctr: an LDS counter): one
-// LDS atomic per wave.  Every lane of the wave must call it.
-__device__ __forceinline__ int wave_append(bool flag, int32_t* ctr) {
-    const uint64_t mask = __ballot(flag);
-    if (mask == 0) return -1;
-    const int lane = threadIdx.x & 63;
-    int base = 0;
-    if (lane == 0) base = atomicAdd(ctr, __builtin_popcountll(mask));
-    base = __builtin_amdgcn_readfirstlane(base);
-    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-    return flag ? base + (int)rank : -1;
-}
-
-// Bounds on the second-nearest distance of X_i (L in X_i.w, U in nn_u[i]):
-//  L (.x): lower bound on |X_i - t_k| for every target k other than the NN — the cache test's;
-//  U (.y): upper bound on the second-nearest distance — the next search's initial pruning bound.
-// From the second-smallest d² a search saw (every other target has float d² >= sec; the true
-// distance is within sqrt(d²)(1 -/+ 3u)), rounded outwards by 1e-6 (>> the sqrt's own rounding).
-__device__ __forceinline__ float2 lu_from_sec(float sec_d2) {
-    const float r = sqrtf(sec_d2);
-    return make_float2(r * 0.999999f, r * 1.000001f);
-}
-
-// The bounds after X_i moved from o to v (float points): L - |v - o|, U + |v - o|, roundings covered.
-__device__ __forceinline__ float2 move_lu(float2 lu, float ox, float oy, float oz, float vx, float vy, float vz) {
-    const float dx = vx - ox, dy = vy - oy, dz = vz - oz;
-    const float d = sqrtf(dx * dx + dy * dy + dz * dz) * 1.00001f;
-    return make_float2(fmaxf((lu.x - d) * 0.999999f, 0.0f), (lu.y + d) * 1.000001f);
-}
-
-// Lazy source cloud (WorkArgs::lazy_x, PairState::pending): L is never negative (move_lu clamps at 0,
-// lu_from_sec scales a square root), so the sign bit of a stored L marks a point that the search
-// re-wrote after a silent tail — it is at the newer state already.  Every reader of a stored L takes
-// fabsf.
-constexpr uint32_t kLazyFlag = 0x80000000u;
-__device__ __forceinline__ bool l_flagged(float L) { return (__float_as_uint(L) & kLazyFlag) != 0u; }
-
-__device__ __forceinline__ bool cache_hit(float L, float dj2) {
-    return L * L * (1.0f - kCacheMargin) > dj2 * (1.0f + kCacheMargin);
-}
 
 __device__ __forceinline__ void write_corr_t(const WorkArgs& w, const PairArgs& a, int p, int i, float sx, float sy,
                                              float sz, float d2, const float4 t) {
@@ -766,10 +555,6 @@ __device__ __forceinline__ void write_corr_t(const WorkArgs& w, const PairArgs& 
 // fitness pass) and by the F64 update (load_nn); the PCL-numerics update folds X and nn_t.
 __device__ __forceinline__ bool keys_read(const PairArgs& a, int fitness_pass) {
     return fitness_pass || a.kp.numerics != kNumericsPCL;
-}
-
-__device__ __forceinline__ bool pass_wants(int phase, int fitness_pass) {
-    return fitness_pass ? (phase != kPhaseInvalid) : (phase == kPhaseActive);
 }
 
 // The update that follows an NN pass clears the pair's miss bitmap and count (the next test kernel
@@ -893,90 +678,6 @@ __global__ __launch_bounds__(kTestWG) void nn_cache_test_kernel(PairArgs a, Work
 // arbitrary and cannot change any result).  all = 1: every pair the pass wants (first pass / no
 // CACHE), work = its source count.
 constexpr int kOrderWG = 1024;
-constexpr int kOrderBuckets = 32;
-constexpr int kPartBits = 10;  // work item = pair << kPartBits | part (parts of >= 64 misses)
-static_assert(kCacheMaxN / 64 <= (1 << kPartBits), "part field");
-
-struct OrderShared {
-    int32_t bcnt[kOrderBuckets], boff[kOrderBuckets];
-    unsigned long long tot;
-};
-
-// The work list of a pass, built by WG threads of one workgroup: by nn_order_kernel, or (FUSED) by
-// the last workgroup of the fold_update_kernel launch that ran the pass's cached-neighbour test,
-// from the per-pair work words (owork) the other workgroups published — written and read with
-// agent-scope (L1-bypassing, write-through) accesses only, so no cache can hold a stale copy.
-template <int WG, bool FUSED>
-__device__ __forceinline__ void order_items_body(const PairArgs& a, const WorkArgs& w, int npairs, int fitness_pass,
-                                                 int all, int ncu, OrderShared& sh) {
-    const int tid = threadIdx.x;
-    if (tid < kOrderBuckets) sh.bcnt[tid] = 0;
-    if (tid == 0) sh.tot = 0;
-    __syncthreads();
-    auto work_load = [&](int p) -> int {
-        if (FUSED) return __hip_atomic_load(w.owork + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & kMissCount;
-        return !pass_wants(w.state[p].phase, fitness_pass) ? 0 : all ? a.src_n[p] : (w.miss_cnt[p] & kMissCount);
-    };
-    // the thread's first kOrderReg pairs' work loaded once, all in flight (the three passes below
-    // had each waited out their loads: one dependent round trip per pass)
-    constexpr int kOrderReg = 4;
-    int wreg[kOrderReg];
-#pragma unroll
-    for (int k = 0; k < kOrderReg; ++k) wreg[k] = tid + k * WG < npairs ? work_load(tid + k * WG) : 0;
-    auto work = [&](int p) -> int {
-        const int k = (p - tid) / WG;
-        return k < kOrderReg ? wreg[k] : work_load(p);
-    };
-    if (!all && w.part_size > 0) {  // the pass' total work, for the part size below
-        unsigned long long t = 0;
-        for (int p = tid; p < npairs; p += WG) t += (unsigned long long)work(p);
-        t = wave_sum(t);
-        if ((tid & 63) == 0) atomicAdd(&sh.tot, t);
-    }
-    __syncthreads();
-    int32_t* bcnt = sh.bcnt;
-    int32_t* boff = sh.boff;
-    const unsigned long long tot_s = sh.tot;
-    // a heavy pair's misses are cut into parts of part_size (first pass: one part, all queries), so
-    // the few slowly converging pairs with thousands of misses spread over several CUs
-    // (at least part_size, and large enough that the pass has about 2 items per CU: a part costs a
-    // target staging, so only the heavy tail of a light pass is worth cutting)
-    constexpr unsigned long long kIpc = 1;  // the work list's target items per CU (round 6: 1 +0.6 % over 2; 3, 4 slower)
-    const int ps = (!all && w.part_size > 0) ? max(w.part_size, (int)((tot_s + kIpc * ncu - 1) / (kIpc * ncu))) : (1 << 30);
-    auto heavy_parts = [&](int c) { return (c + ps - 1) / ps; };
-    auto heavy_size = [&](int c, int k) { return min(ps, c - k * ps); };
-    for (int p = tid; p < npairs; p += WG) {
-        const int c = work(p);
-        if (w.ticks) w.ticks[32 + p] = (uint64_t)c;  // debug: this pass' work per pair (tools/experiments/miss_hist.py)
-        if (c <= 0) continue;
-        for (int k = 0, np = heavy_parts(c); k < np; ++k) atomicAdd(&bcnt[31 - __builtin_clz((uint32_t)heavy_size(c, k))], 1);
-    }
-    __syncthreads();
-    if (tid == 0) {
-        int run = 0;
-        for (int b = kOrderBuckets - 1; b >= 0; --b) {
-            boff[b] = run;
-            run += bcnt[b];
-        }
-        *w.plist_n = run;
-        *w.queue = 0;
-        w.plist_n[2] = ps == (1 << 30) ? 0 : ps;  // nn_lds_kernel: misses per part (0: whole pairs)
-    }
-    __syncthreads();
-    for (int p = tid; p < npairs; p += WG) {
-        const int c = work(p);
-        if (c > 0)
-            for (int k = 0, np = heavy_parts(c); k < np; ++k)
-                w.plist[atomicAdd(&boff[31 - __builtin_clz((uint32_t)heavy_size(c, k))], 1)] = (p << kPartBits) | k;
-    }
-}
-// (order_items_body: inlined where a call would spill the caller's live registers — fold_update_res_kernel
-// takes its kernel arguments' addresses otherwise)
-template <int WG, bool FUSED>
-__device__ void order_items(const PairArgs& a, const WorkArgs& w, int npairs, int fitness_pass, int all, int ncu,
-                            OrderShared& sh) {
-    order_items_body<WG, FUSED>(a, w, npairs, fitness_pass, all, ncu, sh);
-}
 
 __global__ __launch_bounds__(kOrderWG) void nn_order_kernel(PairArgs a, WorkArgs w, int npairs, int fitness_pass,
                                                             int all, int ncu) {
@@ -1882,279 +1583,6 @@ __global__ __launch_bounds__(kLdsWG) void nn_tile_kernel(PairArgs a, WorkArgs w,
     }
 }
 
-// ---------------------------------------------------------------------------------------------
-// Sequential folds over an LDS chunk, one lane per chain: acc = acc + f[k] for k in [0, len), in
-// that order — exactly the reference loop.  Groups of 32 floats are read 32 elements ahead in two
-// explicit register sets (a/b ping-pong) so the chain runs at the dependent-add latency instead of
-// waiting on each LDS round trip.  TAcc = float (the float chains) or double (MSE / fitness: the
-// float values are widened, as PCL's double accumulators do).
-template <typename TAcc>
-__device__ __forceinline__ void add_group(TAcc& acc, const float4 (&g)[8]) {
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-        acc = acc + (TAcc)g[u].x;
-        acc = acc + (TAcc)g[u].y;
-        acc = acc + (TAcc)g[u].z;
-        acc = acc + (TAcc)g[u].w;
-    }
-}
-
-__device__ __forceinline__ void load_group(float4 (&g)[8], const float* f) {
-#pragma unroll
-    for (int u = 0; u < 8; ++u) g[u] = *reinterpret_cast<const float4*>(f + 4 * u);
-}
-
-// The last < 32 elements of a chain segment: groups of 8 loaded one group ahead, then up to 7 loaded
-// together (a dependent scalar loop would wait out one LDS round trip per element — the panel ends of
-// pass B cut segments at arbitrary positions).  f needs no alignment.
-template <typename TAcc>
-__device__ __forceinline__ TAcc fold_tail(const float* f, int len, TAcc acc) {
-    int k = 0;
-    if (len >= 4) {
-        float a0 = f[0], a1 = f[1], a2 = f[2], a3 = f[3];
-        for (; k + 4 <= len; k += 4) {
-            const int nx = (k + 8 <= len) ? k + 4 : k;  // the next group, or a harmless re-read
-            const float b0 = f[nx], b1 = f[nx + 1], b2 = f[nx + 2], b3 = f[nx + 3];
-            __builtin_amdgcn_sched_barrier(0);
-            acc = acc + (TAcc)a0;
-            acc = acc + (TAcc)a1;
-            acc = acc + (TAcc)a2;
-            acc = acc + (TAcc)a3;
-            a0 = b0;
-            a1 = b1;
-            a2 = b2;
-            a3 = b3;
-        }
-    }
-    const int r = len - k;  // 0..3, loaded together
-    const float v0 = f[k], v1 = f[k + (r > 1 ? 1 : 0)], v2 = f[k + (r > 2 ? 2 : 0)];
-    if (r > 0) acc = acc + (TAcc)v0;
-    if (r > 1) acc = acc + (TAcc)v1;
-    if (r > 2) acc = acc + (TAcc)v2;
-    return acc;
-}
-
-// acc + x.x + x.y + x.z + x.w in that order, each IEEE add as v_add_f32 does it, with acc kept in one
-// register (the tied operand): the allocator had used a consumed group register as the running sum,
-// then copied the next group into place with 16 v_mov per round.
-__device__ __forceinline__ float chain_add4(float acc, const float4& x) {
-    asm("v_add_f32 %0, %1, %0\n\t"
-        "v_add_f32 %0, %2, %0\n\t"
-        "v_add_f32 %0, %3, %0\n\t"
-        "v_add_f32 %0, %4, %0"
-        : "+v"(acc)
-        : "v"(x.x), "v"(x.y), "v"(x.z), "v"(x.w));
-    return acc;
-}
-
-// A panel chain's step over one chunk row (len <= T floats, T a multiple of 8; 16-B aligned): groups
-// of 16 floats in two register sets that trade roles (the next group's four ds_read_b128 issued before
-// this group's 16 dependent adds, as long as the LDS round trip; no register copies: one set carried
-// into the next round had cost 16 v_mov and a full lgkmcnt wait per 16 adds, ~15 cycles per add
-// against ~7), the rest through fold_tail — half fold_seq's registers: the panel fold lanes share
-// their waves' allocation with the fillers.
-__device__ __forceinline__ float fold_row(const float* f, int len, float acc) {
-    int k = 0;
-    if (len >= 32) {
-        float4 a[4], b[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) a[u] = *reinterpret_cast<const float4*>(f + 4 * u);
-        for (; k + 32 <= len; k += 32) {
-#pragma unroll
-            for (int u = 0; u < 4; ++u) b[u] = *reinterpret_cast<const float4*>(f + k + 16 + 4 * u);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                acc = chain_add4(acc, a[u]);
-            }
-            const int nx = (k + 48 <= len) ? k + 32 : k;  // the next group, or a harmless re-read
-#pragma unroll
-            for (int u = 0; u < 4; ++u) a[u] = *reinterpret_cast<const float4*>(f + nx + 4 * u);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                acc = chain_add4(acc, b[u]);
-            }
-        }
-        if (k + 16 <= len) {  // a holds f[k, k + 16)
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                acc = chain_add4(acc, a[u]);
-            }
-            k += 16;
-        }
-    }
-    return k < len ? fold_tail<float>(f + k, len - k, acc) : acc;
-}
-
-constexpr int kFoldAhead = 2;  // groups of 32 floats in flight ahead of the adds (1 or 2)
-template <typename TAcc>
-__device__ __forceinline__ TAcc fold_seq(const float* f, int len, TAcc acc) {
-    int k = 0;
-    if (kFoldAhead >= 2 && len >= 96) {
-        // three register groups in rotation, two loads in flight while a group is summed: 6.4-6.7
-        // cycles per dependent add on gfx950 vs 7.6-9.0 with one group ahead (tools/experiments/chain_bench.hip)
-        float4 a[8], b[8], c[8];
-        load_group(a, f);
-        load_group(b, f + 32);
-        for (; k + 96 <= len; k += 96) {
-            // the loads past this round re-read group 0 harmlessly when nothing follows
-            const int n1 = (k + 128 <= len) ? k + 96 : 0, n2 = (k + 160 <= len) ? k + 128 : 0;
-            load_group(c, f + k + 64);
-            __builtin_amdgcn_sched_barrier(0);
-            add_group(acc, a);
-            load_group(a, f + n1);
-            __builtin_amdgcn_sched_barrier(0);
-            add_group(acc, b);
-            load_group(b, f + n2);
-            __builtin_amdgcn_sched_barrier(0);
-            add_group(acc, c);
-        }
-        // a, b hold [k, k + 32) and [k + 32, k + 64) when they exist
-        if (k + 32 <= len) {
-            add_group(acc, a);
-            k += 32;
-            if (k + 32 <= len) {
-                add_group(acc, b);
-                k += 32;
-            }
-        }
-        return k < len ? fold_tail<TAcc>(f + k, len - k, acc) : acc;
-    }
-    if (len >= 32) {
-        float4 a[8], b[8];
-        load_group(a, f);
-        int apos = 0;  // where `a` was loaded from
-        // sched_barrier: keep each prefetch ahead of the adds it overlaps (the scheduler would
-        // otherwise sink the loads down to their first use and expose the LDS latency again)
-        for (; k + 64 <= len; k += 64) {
-            load_group(b, f + k + 32);
-            __builtin_amdgcn_sched_barrier(0);
-            add_group(acc, a);
-            apos = (k + 96 <= len) ? k + 64 : k;  // next group, or a harmless re-read
-            load_group(a, f + apos);
-            __builtin_amdgcn_sched_barrier(0);
-            add_group(acc, b);
-        }
-        if (k + 32 <= len) {
-            if (apos != k) load_group(a, f + k);
-            add_group(acc, a);
-            k += 32;
-        }
-    }
-    return k < len ? fold_tail<TAcc>(f + k, len - k, acc) : acc;
-}
-
-// fold_seq with the chain switched at element xa (a wave-uniform multiple of 32): groups before it go
-// to acc, the rest to acc2 — a panel end of pass B inside a chunk (the fillers padded the ending
-// panel to xa with +0).  One three-group rotation over the whole row: the loads stay in flight across
-// the switch, which is a scalar branch per group.
-template <typename TAcc>
-__device__ __forceinline__ void fold_seq_switch(const float* f, int len, int xa, TAcc& acc, TAcc& acc2) {
-    xa = __builtin_amdgcn_readfirstlane(xa);
-    auto add = [&](int k, const float4 (&g)[8]) __attribute__((always_inline)) {
-        if (k < xa)
-            add_group(acc, g);
-        else
-            add_group(acc2, g);
-    };
-    int k = 0;
-    if (len >= 96) {
-        float4 a[8], b[8], c[8];
-        load_group(a, f);
-        load_group(b, f + 32);
-        for (; k + 96 <= len; k += 96) {
-            const int n1 = (k + 128 <= len) ? k + 96 : 0, n2 = (k + 160 <= len) ? k + 128 : 0;
-            load_group(c, f + k + 64);
-            __builtin_amdgcn_sched_barrier(0);
-            add(k, a);
-            load_group(a, f + n1);
-            __builtin_amdgcn_sched_barrier(0);
-            add(k + 32, b);
-            load_group(b, f + n2);
-            __builtin_amdgcn_sched_barrier(0);
-            add(k + 64, c);
-        }
-        if (k + 32 <= len) {
-            add(k, a);
-            k += 32;
-            if (k + 32 <= len) {
-                add(k, b);
-                k += 32;
-            }
-        }
-    } else {
-        for (; k + 32 <= len; k += 32) {
-            float4 a[8];
-            load_group(a, f + k);
-            add(k, a);
-        }
-    }
-    if (k < len) {  // the last < 32 elements belong to the second chain (xa <= the last group's start)
-        if (k < xa)
-            acc = fold_tail<TAcc>(f + k, len - k, acc);
-        else
-            acc2 = fold_tail<TAcc>(f + k, len - k, acc2);
-    }
-}
-
-// fold_seq over row[a, b) of a 16-B aligned LDS row (a, b wave-uniform): up to 3 leading elements
-// until row + a is aligned, then fold_seq.
-template <typename TAcc>
-__device__ __forceinline__ TAcc fold_span(const float* row, int a, int b, TAcc acc) {
-    const int a4 = min(b, (a + 3) & ~3);
-    if (a < a4) acc = fold_tail<TAcc>(row + a, a4 - a, acc);
-    return a4 < b ? fold_seq<TAcc>(row + a4, b - a4, acc) : acc;
-}
-
-// The double chains (PCL's MSE sum and getFitnessScore) over values the fillers stored as doubles:
-// the widening (exact) is done by the filler waves, so the fold lane only adds — a v_cvt_f64_f32 in
-// front of every dependent v_add_f64 had put the chain at ~13.5 cycles per element.  Groups of 16
-// doubles (8 x b128), three in rotation as in fold_seq.
-__device__ __forceinline__ void load_group_d(double2 (&g)[8], const double* f) {
-#pragma unroll
-    for (int u = 0; u < 8; ++u) g[u] = *reinterpret_cast<const double2*>(f + 2 * u);
-}
-__device__ __forceinline__ void add_group_d(double& acc, const double2 (&g)[8]) {
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-        acc = acc + g[u].x;
-        acc = acc + g[u].y;
-    }
-}
-__device__ __forceinline__ double fold_seq_d(const double* f, int len, double acc) {
-    int k = 0;
-    if (len >= 48) {
-        double2 a[8], b[8], c[8];
-        load_group_d(a, f);
-        load_group_d(b, f + 16);
-        for (; k + 48 <= len; k += 48) {
-            // the loads past this round re-read group 0 harmlessly when nothing follows
-            const int n1 = (k + 64 <= len) ? k + 48 : 0, n2 = (k + 80 <= len) ? k + 64 : 0;
-            load_group_d(c, f + k + 32);
-            __builtin_amdgcn_sched_barrier(0);
-            add_group_d(acc, a);
-            load_group_d(a, f + n1);
-            __builtin_amdgcn_sched_barrier(0);
-            add_group_d(acc, b);
-            load_group_d(b, f + n2);
-            __builtin_amdgcn_sched_barrier(0);
-            add_group_d(acc, c);
-        }
-        // a, b hold [k, k + 16) and [k + 16, k + 32) when they exist
-        if (k + 16 <= len) {
-            add_group_d(acc, a);
-            k += 16;
-            if (k + 16 <= len) {
-                add_group_d(acc, b);
-                k += 16;
-            }
-        }
-    }
-    for (; k < len; ++k) acc = acc + f[k];
-    return acc;
-}
-
 // Brute-force path: the correspondence arrays from the merged NN keys (the pruned kernel writes
 // them itself).
 __global__ __launch_bounds__(256) void corr_kernel(PairArgs a, WorkArgs w) {
@@ -2312,30 +1740,6 @@ __device__ __forceinline__ void transform_pair(const WorkArgs& w, int p, int n, 
 
 constexpr int kTailPer = 4;  // fused test: points per thread per pipelined group
 
-// ---------------------------------------------------------------------------------------------
-// The cached-neighbour test of one pair by one workgroup of WG threads (the update's fused tail, and
-// the fitness pass inside fitness_prep_kernel): the same work as nn_cache_test_kernel for the pair —
-// X_i's new position (FROM_SRC: T·input_i, the fitness pass' final·input; else T·X_i, the deferred
-// transformCloud(T_inc)), the bounds moved by |new − old|, the test against the cached NN; a miss
-// sets its bit in the pair's bitmap (built in LDS: `need`, zeroed by the caller) and appends its
-// search record; the fitness pass also writes a hit's key (finish_kernel's fitness reads them).
-// kPer points per thread per group, software-pipelined: the next group's loads are issued before
-// this group's stores, so the stores drain while the loads are in flight (a load issued after a store
-// would wait behind it on vmcnt).
-// Per point: X (.w = L) and nn_t (.w = target position | sorted position) read, U read (and the
-// input point, FROM_SRC); X and U written (the fitness pass: neither bounds nor X, unless the aligned
-// cloud is asked for).  The iteration passes write no key: nothing reads one before the fitness pass
-// — the update folds recompute d² from X and nn_t, and the next search seeds from the record.
-// The miss records stay in LDS (lv / lm, the first lcap of them) and are placed at their ranks in the
-// pair's query list (qv / qm) at the end; a pair with more misses than lcap leaves its whole list in
-// sq / sm with its bitmap, flagged kMissUnranked, for the search to place.
-// The first point group's loads (kPer points per thread: X, the NN record, U) — issued by the update
-// before its solve, so their latency hides behind thread 0's SVD (they do not depend on T_inc).
-template <int kPer>
-struct TailFirst {
-    float4 v[kPer], t[kPer];
-    float U[kPer];
-};
 // SUMS: the tail also folds the next pass A's Σs (pair_cache_test); wave 0 folds, waves 1.. test, in
 // index order.
 template <int WG, int kPer, bool SUMS = false>
@@ -2360,272 +1764,6 @@ __device__ __forceinline__ void tail_prefetch(const WorkArgs& w, int p, int n, T
     }
 }
 
-// A fold wave's issue priority: its sequential chain is one dependent add after
-// another, and the SIMD's other waves (fillers, the fused test's workers) otherwise take the issue
-// slots between them.
-__device__ __forceinline__ void fold_prio(bool hi) {
-    if (hi)
-        __builtin_amdgcn_s_setprio(3);
-    else
-        __builtin_amdgcn_s_setprio(0);
-}
-
-// SUMS (the update's tail, eligible pairs): the next pass A's Σs folded here, in index order, over the X
-// the test writes — wave 0 lanes 0..2 fold, waves 1.. test (groups of (WG - 64) * kPer points, first
-// to last, each group's new coordinates staged in `stg`: two buffers of 3 rows of kSumRow floats); the sums go to
-// sums_out[0..2] (the pair state) with *sums_ok = 1.
-constexpr int kSumPer = 2;  // the Σs tail's points per worker and group (4: 185 vs 179.5 us per update)
-constexpr int kSumRow = 192 * kSumPer + 4;  // staged points per group (192 workers x kSumPer) + pad
-constexpr int kSumBuf = 3 * kSumRow;        // one group's staging; two alternate (double buffer)
-// The end of a pair's cached-neighbour test (pair_cache_test; res_update_pair's tail): the per-wave
-// counts and work counters, then the miss records — lv / lm in LDS (the first lcap; beyond, sq / sm)
-// — placed at their ranks in the pair's query list, or the whole list left unranked in sq / sm with
-// the bitmap when it overflowed.  Returns the pair's misses.
-template <int WG>
-__device__ __forceinline__ int test_place(const WorkArgs& w, int p, int n, int hits, int misses, uint32_t* need,
-                                          int32_t* pre, float4* lv, uint2* lm, int lcap, int32_t* wcnt, bool fitness,
-                                          uint64_t* stamp) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t xs = (int64_t)p * w.x_stride;
-    hits = wave_sumi(hits);
-    misses = wave_sumi(misses);
-    if (lane == 0) {
-        wcnt[wave] = misses;
-        count_add(w.evals, 0, (unsigned long long)hits);
-        count_add(w.evals, 2, (unsigned long long)hits);
-        count_add(w.evals, 3, (unsigned long long)(hits + misses));
-        if (!fitness) {  // ... of which in an update's tail
-            count_add(w.evals, 5, (unsigned long long)(hits + misses));
-            count_add(w.evals, 6, (unsigned long long)hits);
-        }
-    }
-    __syncthreads();
-    if (stamp && tid == 0) *stamp = __builtin_amdgcn_s_memrealtime();  // diagnostic: the test's end
-    int tot = 0;
-    for (int k = 0; k < WG / 64; ++k) tot += wcnt[k];
-    if (tot == 0) {
-        if (tid == 0) w.miss_cnt[p] = 0;
-        return 0;
-    }
-    const int nwords = (n + 31) >> 5;
-    if (tot > lcap) {
-        // more misses than LDS records (the few slowly converging pairs): the whole list goes to
-        // sq / sm and the bitmap to global memory, and the search places it — a read-back of the
-        // overflow here sat on this workgroup's end, which sets the update's launch time
-        for (int k = tid; k < lcap; k += WG) {
-            w.sq[xs + k] = lv[k];
-            w.sm[xs + k] = lm[k];
-        }
-        uint32_t* gneed = w.need + (int64_t)p * w.need_stride;
-        for (int k = tid; k < nwords; k += WG) gneed[k] = need[k];
-        if (tid == 0) w.miss_cnt[p] = tot | kMissUnranked;
-        return tot;
-    }
-    // Rank placement: the search reads its item's queries in sorted-position order (a run of 64
-    // consecutive ones is a compact box), so every miss record goes to its rank in the bitmap — the
-    // word's prefix + the set bits below it.  Done here, where the workgroup owns the whole bitmap,
-    // instead of in the search, where it put two barriers and three dependent global round trips in
-    // front of every work item.  Word prefixes: wave 0, kNeedWords / 64 words per lane.
-    if (wave == 0) {
-        constexpr int kW = kNeedWords / 64;
-        int c[kW], sum = 0;
-#pragma unroll
-        for (int j = 0; j < kW; ++j) {
-            const int wd = lane * kW + j;
-            c[j] = wd < nwords ? __builtin_popcount(need[wd]) : 0;
-            sum += c[j];
-        }
-        int incl = sum;
-        incl = (int)wave_scan_incl((uint32_t)incl);  // (DPP)
-        int run = incl - sum;
-#pragma unroll
-        for (int j = 0; j < kW; ++j) {
-            pre[lane * kW + j] = run;
-            run += c[j];
-        }
-    }
-    if (tid == 0) w.miss_cnt[p] = tot;
-    __syncthreads();
-    float4* qv = w.qv + xs;
-    uint2* qm = w.qm + xs;
-    auto get = [&](int k, float4& r, uint2& m) {  // (tot <= lcap: every record is in LDS)
-        k = min(k, tot - 1);
-        r = lv[k];
-        m = lm[k];
-    };
-    // (unconditional: a slot past the list re-read record tot - 1 and writes its very bytes to its
-    // very rank again)
-    auto put = [&](const float4 r, const uint2& m) {
-        const uint32_t sp = min(m.y, (uint32_t)(n - 1));
-        const int rk = pre[sp >> 5] + __builtin_popcount(need[sp >> 5] & ((1u << (sp & 31)) - 1u));
-        qv[rk] = r;
-        const uint2 mm = make_uint2((m.x & kNtIdxMask) | (sp << kNtPosShift), m.x >> kNtPosShift);
-        uint64_t* const qmk = reinterpret_cast<uint64_t*>(&qm[rk]);
-        *qmk = (uint64_t)mm.x | ((uint64_t)mm.y << 32);
-    };
-    for (int k0 = tid; k0 < tot; k0 += 4 * WG) {
-        float4 r0, r1, r2, r3;  // (named, not an array: an array went to scratch)
-        uint2 m0, m1, m2, m3;
-        get(k0, r0, m0);  // all loads of the round first
-        get(k0 + WG, r1, m1);
-        get(k0 + 2 * WG, r2, m2);
-        get(k0 + 3 * WG, r3, m3);
-        put(r0, m0);
-        put(r1, m1);
-        put(r2, m2);
-        put(r3, m3);
-    }
-    return tot;
-}
-
-template <int WG, int kPer, bool FROM_SRC, bool SUMS = false>
-__device__ __forceinline__ int pair_cache_test(const PairArgs& a, const WorkArgs& w, int p, int n, const float (&T)[16],
-                                                uint32_t* need, int32_t* pre, float4* lv, uint2* lm, int lcap,
-                                                int32_t* mcount, int32_t* wcnt, bool fitness, uint64_t* stamp = nullptr,
-                                                const TailFirst<kPer>* first = nullptr, float* stg = nullptr,
-                                                float* sums_out = nullptr, int32_t* sums_ok = nullptr,
-                                                const float* Tp = nullptr, bool silent = false) {
-    // Lazy source cloud (WorkArgs::lazy_x; both workgroup-uniform, the update's tail only):
-    //  silent: X', L', U' are formed and tested as ever but not stored — the caller records T as the
-    //          pair's T_pend; the stored triple of every point stays consistent at the older state.
-    //  Tp:     the pair is pending (the previous tail was silent, Tp = its T): an unflagged point is first
-    //          brought to the state that tail would have stored — Tp * X, the bounds moved by that step, the
-    //          very expressions it evaluated — a flagged one (re-written by the search since) is there
-    //          already; then this tail's own step, stored with a positive L.
-    static_assert(!SUMS || (WG - 64) * kPer <= kSumRow - 4, "staging rows");
-    static_assert(!(FROM_SRC && SUMS), "the fitness pass folds no sums");
-    float Tq[16];
-#pragma unroll
-    for (int q = 0; q < 16; ++q) Tq[q] = (!FROM_SRC && !SUMS && Tp) ? uload(Tp + q) : 0.0f;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    constexpr int WW = SUMS ? WG - 64 : WG;  // threads that test
-    const bool worker = !SUMS || wave >= 1;
-    const int wt = SUMS ? tid - 64 : tid;
-    const int64_t xs = (int64_t)p * w.x_stride;
-    float4* X = w.X + xs;
-    float* uu = w.nn_u + xs;
-    const float4* nt = w.nn_t + xs;
-    const float4* src = FROM_SRC ? a.src + a.src_off[p] : nullptr;
-    NNKey* key = w.nn_key + xs;
-    constexpr int kStep = WW * kPer;
-    int hits = 0, misses = 0;
-    float fs = -0.0f;  // SUMS: wave 0 lane k's Σs chain (Eigen's rowwise().sum(): from the first element)
-    float4 v[kPer], t[kPer], sv[kPer];
-    float U[kPer];
-    auto load = [&](int i0, float4 (&vv)[kPer], float4 (&tt)[kPer], float (&UU)[kPer], float4 (&ss)[kPer]) {
-#pragma unroll
-        for (int e = 0; e < kPer; ++e) {
-            const int i = min(i0 + e * WW + wt, n - 1);
-            vv[e] = X[i];
-            tt[e] = nt[i];
-            UU[e] = uu[i];
-            if (FROM_SRC) ss[e] = src[i];
-        }
-    };
-    // Groups are visited last to first: the update's pass B has just streamed the
-    // pair's X and nn_t front to back, so its most recently fetched lines — the ones still in the
-    // L2 / MALL — are the pair's last ones.  (The folds must run in index order; the test may run in
-    // any.)
-    const int ngrp = (n + kStep - 1) / kStep;
-    auto grp0 = [&](int g) { return (!SUMS ? ngrp - 1 - g : g) * kStep; };
-    if (ngrp > 0 && worker) {
-        if (first && !FROM_SRC) {
-#pragma unroll
-            for (int e = 0; e < kPer; ++e) {
-                v[e] = first->v[e];
-                t[e] = first->t[e];
-                U[e] = first->U[e];
-            }
-        } else {
-            load(grp0(0), v, t, U, sv);
-        }
-    }
-    for (int g = 0; g < ngrp; ++g) {
-        const int i0 = grp0(g);
-        // SUMS: group g is staged in buffer g & 1 while the fold wave folds group g - 1 from the other;
-        // the fold wave reaches barrier g only after folding g - 2, whose buffer group g reuses
-        float* sg = stg + (g & 1) * kSumBuf;
-        if (SUMS && !worker) {  // the fold wave: the group's staged coordinates, in index order
-            __syncthreads();    // group g staged
-            fold_prio(true);
-            if (lane < 3) fs = fold_row(sg + lane * kSumRow, min(kStep, n - i0), fs);
-            fold_prio(false);
-            continue;
-        }
-        float4 vn[kPer], tn[kPer], sn[kPer];
-        float Un[kPer];
-        if (g + 1 < ngrp) load(grp0(g + 1), vn, tn, Un, sn);
-#pragma unroll
-        for (int e = 0; e < kPer; ++e) {
-            const int i = i0 + e * WW + wt;
-            const bool valid = i < n;
-            float4 o = v[e];
-            float4 b = v[e];  // the point and its bounds before this step (.w = L)
-            b.w = fabsf(v[e].w);
-            float Ub = U[e];
-            if (!FROM_SRC && !SUMS && Tp) {
-                float qx, qy, qz;
-                xform_pt(Tq, b.x, b.y, b.z, qx, qy, qz);
-                const float2 Lq = move_lu(make_float2(b.w, Ub), b.x, b.y, b.z, qx, qy, qz);
-                const bool newer = l_flagged(v[e].w);
-                b.x = newer ? b.x : qx;
-                b.y = newer ? b.y : qy;
-                b.z = newer ? b.z : qz;
-                b.w = newer ? b.w : Lq.x;
-                Ub = newer ? Ub : Lq.y;
-            }
-            if (FROM_SRC)
-                xform_pt(T, sv[e].x, sv[e].y, sv[e].z, o.x, o.y, o.z);  // final * input
-            else
-                xform_pt(T, b.x, b.y, b.z, o.x, o.y, o.z);  // PCL transformCloud, in place
-            const float2 Lm = move_lu(make_float2(b.w, Ub), b.x, b.y, b.z, o.x, o.y, o.z);
-            o.w = Lm.x;
-            const float d2 = l2_simple(o.x, o.y, o.z, t[e].x, t[e].y, t[e].z);
-            const bool hit = valid & cache_hit(Lm.x, d2);
-            // (the fitness pass: no later pass reads the bounds, and X only for the aligned output —
-            // the misses' search records carry their own coordinates)
-            if (valid && (!fitness || a.aligned) && !silent) X[i] = o;
-            if (valid && !fitness && !silent) uu[i] = Lm.y;
-            if (SUMS && valid) {
-                sg[e * WW + wt] = o.x;
-                sg[kSumRow + e * WW + wt] = o.y;
-                sg[2 * kSumRow + e * WW + wt] = o.z;
-            }
-            const int k = wave_append(valid && !hit, mcount);
-            if (hit) {
-                // the fitness pass' keys are read for their d² only (finish_kernel): a hit's index
-                // bits carry its NN's sorted position, no gather of the original index
-                if (fitness) key[i] = make_key(d2, nt_tpos(t[e].w));
-                ++hits;
-            } else if (valid) {
-                const uint32_t sp = nt_pos(t[e].w);
-                atomicOr(&need[sp >> 5], 1u << (sp & 31));
-                if (k < lcap) {
-                    lv[k] = make_float4(o.x, o.y, o.z, Lm.y);
-                    *reinterpret_cast<uint64_t*>(&lm[k]) =
-                        (uint64_t)((uint32_t)i | (nt_tpos(t[e].w) << kNtPosShift)) | ((uint64_t)sp << 32);
-                } else {
-                    put_miss(w, p, k, sp, i, o.x, o.y, o.z, Lm.y, nt_tpos(t[e].w));
-                }
-                ++misses;
-            }
-        }
-#pragma unroll
-        for (int e = 0; e < kPer; ++e) {
-            v[e] = vn[e];
-            t[e] = tn[e];
-            U[e] = Un[e];
-            if (FROM_SRC) sv[e] = sn[e];
-        }
-        if (SUMS) __syncthreads();  // group g staged
-    }
-    if (SUMS && wave == 0 && lane < 3) {
-        sums_out[lane] = fs;
-        if (lane == 0 && *sums_ok != -1) *sums_ok = 1;
-    }
-    return test_place<WG>(w, p, n, hits, misses, need, pre, lv, lm, lcap, wcnt, fitness, stamp);
-}
-
 // ---------------------------------------------------------------------------------------------
 // fold_update_kernel (PCL numerics): one workgroup per active pair.  Bit-exact float restatement
 // of TransformationEstimationSVD (use_umeyama, Scalar = float) and calculateMSE: every sum is the
@@ -2642,12 +1780,7 @@ __device__ __forceinline__ int pair_cache_test(const PairArgs& a, const WorkArgs
 // Rejected correspondences contribute the fold's identity (-0.0f / +0), i.e. nothing.
 constexpr int kFoldWG = 256;
 constexpr int kFoldWaves = kFoldWG / 64;
-constexpr int kFoldChunkP = 512;  // points per LDS chunk of the fold passes
 
-// Each fold chain's row is padded by kFoldPad floats: unpadded, rows 2 KB apart start on the same
-// LDS bank, and the 7-9 fold lanes' ds_read_b128 of one column were a 7-9-way bank conflict on every
-// read.  Padded by 16 B they take distinct banks.
-constexpr int kFoldPad = 4;
 constexpr int kFoldRow = kFoldChunkP + kFoldPad;
 
 // the fused test's LDS miss records (24 B each) after the bitmap and its prefixes, in the fold buffers
@@ -4464,221 +3597,6 @@ __global__ __launch_bounds__(kUpdWG) void update_f64_kernel(PairArgs a, WorkArgs
 }
 
 // ---------------------------------------------------------------------------------------------
-// fitness_prep_kernel: X := final * input (Registration::getFitnessScore / align's output).
-// test (cached-neighbour plan): the fitness pass' cached-neighbour test runs here too, by the pair's
-// workgroup (pair_cache_test), instead of as nn_cache_test_kernel after it — one read of X, U, nn_t
-// and the input per point, no launch of its own.
-constexpr int kPrepWG = 256;
-constexpr int kPrepRecs = 1024;  // the fitness test's LDS miss records (the fitness pass misses ~1 %)
-__global__ __launch_bounds__(kPrepWG) void fitness_prep_kernel(PairArgs a, WorkArgs w, int test) {
-    const int p = xcd_remap(blockIdx.x, gridDim.x);
-    const PairState& st = w.state[p];
-    if (st.phase == kPhaseInvalid) return;
-    __shared__ float Tf[16];
-    __shared__ uint32_t need[kNeedWords];
-    __shared__ int32_t pre[kNeedWords];
-    __shared__ float4 lv[kPrepRecs];
-    __shared__ uint2 lm[kPrepRecs];
-    __shared__ int32_t mcount, wcnt[kPrepWG / 64];
-    const int n = a.src_n[p];
-    if (threadIdx.x < 16) Tf[threadIdx.x] = st.final_T[threadIdx.x];
-    if (test && w.nn_u) {
-        for (int k = threadIdx.x; k < (n + 31) >> 5; k += kPrepWG) need[k] = 0u;
-        if (threadIdx.x == 0) mcount = 0;
-        __syncthreads();
-        float T[16];
-#pragma unroll
-        for (int q = 0; q < 16; ++q) T[q] = Tf[q];
-        pair_cache_test<kPrepWG, 4, true>(a, w, p, n, T, need, pre, lv, lm, kPrepRecs, &mcount, wcnt, true);
-        return;
-    }
-    __syncthreads();
-    const float4* src = a.src + a.src_off[p];
-    float4* X = w.X + (int64_t)p * w.x_stride;
-    float* uu = w.nn_u ? w.nn_u + (int64_t)p * w.x_stride : nullptr;
-    // (w.seed_next: the fitness pass's seed keys too — see transform_pair)
-    const bool seed = w.seed_next && w.corr && a.kp.compute_fitness;
-    NNKey* key = w.nn_key + (int64_t)p * w.x_stride;
-    const float4* C = w.corr ? w.corr + (int64_t)p * w.x_stride * 2 : nullptr;
-    for (int i = threadIdx.x; i < n; i += kPrepWG) {
-        const float4 s = src[i];
-        float4 o = s;
-        xform_pt(Tf, s.x, s.y, s.z, o.x, o.y, o.z);
-        if (seed) {
-            const float4 t = C[2 * i + 1];
-            key[i] = make_key(l2_simple(o.x, o.y, o.z, t.x, t.y, t.z), (uint32_t)key_idx(key[i]));
-        }
-        if (uu) {  // X still holds the last NN pass's points (a deferred transform never ran), .w = L
-            const float4 old = X[i];
-            const float2 Lm = move_lu(make_float2(fabsf(old.w), uu[i]), old.x, old.y, old.z, o.x, o.y, o.z);
-            o.w = Lm.x;
-            uu[i] = Lm.y;
-        }
-        X[i] = o;
-    }
-}
-
-// finish_kernel: fitness = mean of d² over d² <= max_range (double), results, aligned output.
-constexpr int kFinWG = 256;
-__global__ __launch_bounds__(kFinWG) void finish_kernel(PairArgs a, WorkArgs w) {
-    const int p = xcd_remap(blockIdx.x, gridDim.x);
-    const PairState& st = w.state[p];
-    const int n = a.src_n[p];
-    const int64_t slot0 = (int64_t)p * w.x_stride;
-    const bool have = st.phase != kPhaseInvalid && a.kp.compute_fitness && n > 0;
-    // Registration::getFitnessScore: sequential double sum over points with d² <= max_range, in
-    // index order, by wave 0 lane 0 over LDS chunks that waves 1..3 stage (double buffer); points
-    // beyond max_range contribute +0 (a no-op on the non-negative running sum); the count is an
-    // exact integer reduction.  Bit-identical to the reference loop.
-    __shared__ double chunk[2][kFoldChunkP];  // (doubles: the fold lane only adds, fold_seq_d)
-    __shared__ int32_t fcnt_w[kFinWG / 64];
-    __shared__ uint64_t fsum_w[kFinWG / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    double fsum = 0.0;
-    int fcnt = 0;
-    // Exact parallel form of the same sum.  Every term is a float widened to double, so every term is
-    // an integer multiple of 2^e, e = the lowest set bit's exponent over the nonzero terms.  When the
-    // exact total S is below 2^(e + 53), every partial sum of the non-negative terms is a multiple of
-    // 2^e below 2^(e + 53), i.e. a double: the sequential loop never rounds and returns S itself.  S is
-    // then an integer sum in units of 2^e (associative), saturated at 2^53; otherwise (a span of more
-    // than 53 bits between the smallest term's last bit and the total) the sequential fold below runs.
-    // Batches of at least kFinExactMaxPairs pairs keep the sequential fold only: their chains overlap
-    // across the pairs, and the exact attempt measured slower there (C3: 43 -> 63 us per batch; a
-    // pair whose span test fails pays both forms).
-    constexpr int kFinExactMaxPairs = 256;
-    bool exact = false;
-    if (have && (int)gridDim.x < kFinExactMaxPairs) {
-        constexpr uint64_t kSat = 1ull << 53;
-        // the values: in registers for clouds of at most kFinWG * kFinPer points (every load in flight
-        // at once, one read of the keys), else re-read per pass; NaN = no point (never in range)
-        constexpr int kFinPer = 32;
-        const bool reg = n <= kFinWG * kFinPer;
-        float v[kFinPer];
-        if (reg) {
-#pragma unroll
-            for (int k = 0; k < kFinPer; ++k) {
-                const int i = threadIdx.x + k * kFinWG;
-                v[k] = i < n ? key_d2(w.nn_key[slot0 + i]) : __int_as_float(0x7fc00000);
-            }
-        }
-        auto each = [&](auto&& f) {
-            if (reg) {
-#pragma unroll
-                for (int k = 0; k < kFinPer; ++k) f(v[k]);
-            } else {
-                for (int i = threadIdx.x; i < n; i += kFinWG) f(key_d2(w.nn_key[slot0 + i]));
-            }
-        };
-        int emin = INT_MAX;
-        each([&](float d2) {
-            const double x = (double)d2;
-            if (x <= a.kp.fit_max_range) {
-                ++fcnt;
-                if (x > 0.0) {
-                    const uint64_t b = (uint64_t)__double_as_longlong(x);
-                    const int ex = (int)((b >> 52) & 0x7ff);
-                    const uint64_t mant = (b & ((1ull << 52) - 1)) | (1ull << 52);
-                    emin = min(emin, ex - 1075 + (int)__builtin_ctzll(mant));
-                }
-            }
-        });
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            emin = min(emin, __shfl_xor(emin, off, 64));
-            fcnt += __shfl_xor(fcnt, off, 64);
-        }
-        if (lane == 0) {
-            fcnt_w[wave] = fcnt;
-            fsum_w[wave] = (uint64_t)(uint32_t)emin;
-        }
-        __syncthreads();
-        fcnt = 0;
-        emin = INT_MAX;
-        for (int k = 0; k < kFinWG / 64; ++k) {
-            fcnt += fcnt_w[k];
-            emin = min(emin, (int)(uint32_t)fsum_w[k]);
-        }
-        __syncthreads();  // (fsum_w reused below)
-        uint64_t S = 0;
-        if (emin != INT_MAX) {
-            each([&](float d2) {
-                const double x = (double)d2;
-                if (x <= a.kp.fit_max_range && x > 0.0) {
-                    const uint64_t b = (uint64_t)__double_as_longlong(x);
-                    const int ex = (int)((b >> 52) & 0x7ff);
-                    const uint64_t mant = (b & ((1ull << 52) - 1)) | (1ull << 52);
-                    // x = mant * 2^(ex - 1075); below 2^(emin + 53) iff ex - 1023 - emin <= 52, and then
-                    // x / 2^emin = mant >> (emin + 1075 - ex), a shift by at most ctz(mant): exact
-                    const uint64_t t = (ex - 1023 - emin <= 52) ? (mant >> (emin + 1075 - ex)) : kSat;
-                    S = (S + t < kSat) ? S + t : kSat;
-                }
-            });
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) S = min(S + __shfl_xor(S, off, 64), kSat);
-            if (lane == 0) fsum_w[wave] = S;
-            __syncthreads();
-            S = 0;
-            for (int k = 0; k < kFinWG / 64; ++k) S = min(S + fsum_w[k], kSat);
-        }
-        if (S < kSat) {
-            exact = true;
-            fsum = emin == INT_MAX ? 0.0 : ldexp((double)S, emin);
-        }
-    }
-    if (have && !exact) {
-        fcnt = 0;
-        __syncthreads();  // (fcnt_w reused)
-        const int nch = (n + kFoldChunkP - 1) / kFoldChunkP;
-        auto fill = [&](int c) {
-            const int base = c * kFoldChunkP, len = min(kFoldChunkP, n - base);
-            for (int o = threadIdx.x - 64; o < len; o += kFinWG - 64) {
-                const float d2 = key_d2(w.nn_key[slot0 + base + o]);  // (d² only: see WorkArgs::nn_key)
-                const bool in = (double)d2 <= a.kp.fit_max_range;
-                chunk[c & 1][o] = in ? (double)d2 : 0.0;
-                fcnt += in ? 1 : 0;
-            }
-        };
-        if (wave >= 1) fill(0);
-        for (int c = 0; c < nch; ++c) {
-            __syncthreads();
-            if (wave == 0) {
-                if (lane == 0) fsum = fold_seq_d(chunk[c & 1], min(kFoldChunkP, n - c * kFoldChunkP), fsum);
-            } else if (c + 1 < nch) {
-                fill(c + 1);
-            }
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) fcnt += __shfl_xor(fcnt, off, 64);
-        if (lane == 0) fcnt_w[wave] = fcnt;
-        __syncthreads();
-        fcnt = 0;
-        for (int k = 0; k < kFinWG / 64; ++k) fcnt += fcnt_w[k];
-    }
-    if (a.aligned && st.phase != kPhaseInvalid) {
-        const float4* src = a.src + a.src_off[p];
-        const float4* X = w.X + (int64_t)p * w.x_stride;
-        float4* out = a.aligned + a.src_off[p];
-        for (int i = threadIdx.x; i < n; i += kFinWG) {
-            float4 v = X[i];
-            v.w = src[i].w;  // intensity copied through
-            out[i] = v;
-        }
-    }
-    if (threadIdx.x == 0) {
-        Result r;
-        for (int k = 0; k < 16; ++k) r.T[k] = st.final_T[k];
-        r.fitness = (have && fcnt > 0) ? fsum / fcnt : DBL_MAX;
-        r.iterations = st.iterations;
-        r.converged = st.phase == kPhaseConverged ? 1 : 0;
-        r.status = st.status;
-        r.convergence_state = st.conv_state;
-        r.n_correspondences = st.ncorr;
-        r.reserved = 0;
-        a.results[p] = r;
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
 // solo_kernel: one pair's whole registration by one 1024-thread workgroup — the unbatched plan for
 // targets of at most kLdsTargets points (C1, C2: the node's per-frame call,
 // iterative_closest_point.cpp:510-521), after init_kernel and index_kernel.  The pair's targets and
@@ -4980,32 +3898,6 @@ __global__ __launch_bounds__(kSoloWG) void solo_kernel(PairArgs a, WorkArgs w, i
     }
 }
 
-// Test hook: the device float Umeyama rotation for k sigma matrices (one thread each).
-__global__ void rot_f32_kernel(const float* sigma, float* R, int k) {
-    const int i = blockIdx.x * 64 + threadIdx.x;
-    if (i >= k) return;
-    float sg[9], Ri[9];
-#pragma unroll
-    for (int e = 0; e < 9; ++e) sg[e] = sigma[9 * i + e];
-    umeyama_rotation_f32_reg(sg, Ri);
-#pragma unroll
-    for (int e = 0; e < 9; ++e) R[9 * i + e] = Ri[e];
-}
-
-hipError_t launch_rot_f32(const float* sigma, float* R, int k, hipStream_t st) {
-    hipLaunchKernelGGL(rot_f32_kernel, dim3((k + 63) / 64), dim3(64), 0, st, sigma, R, k);
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------------------------
-hipError_t launch_init(const PairArgs& a, const WorkArgs& w, int npairs, hipStream_t st) {
-    if (npairs < 64)
-        hipLaunchKernelGGL(init_kernel<1024>, dim3(npairs), dim3(1024), 0, st, a, w);
-    else
-        hipLaunchKernelGGL(init_kernel<256>, dim3(npairs), dim3(256), 0, st, a, w);
-    return hipGetLastError();
-}
-
 hipError_t launch_nn(int q, bool packed, const PairArgs& a, const WorkArgs& w, int npairs, int max_n,
                      int fitness_pass, hipStream_t st) {
     const int per_block = kNNWG * q;
@@ -5159,18 +4051,6 @@ hipError_t launch_solo(const PairArgs& a, const WorkArgs& w, int npairs, int max
         !w.qm || !w.sq || !w.sm || !w.need || !w.miss_cnt || npairs <= 0 || iters <= 0)
         return hipErrorInvalidValue;
     hipLaunchKernelGGL(solo_kernel, dim3(npairs), dim3(kSoloWG), 0, st, a, w, iters);
-    return hipGetLastError();
-}
-
-hipError_t launch_fitness_prep(const PairArgs& a, const WorkArgs& w, int npairs, hipStream_t st, int test) {
-    if (test && (!w.nn_u || !w.need || !w.miss_cnt || !w.nn_t || !w.sq || !w.tsort || w.x_stride > kCacheMaxN))
-        return hipErrorInvalidValue;
-    hipLaunchKernelGGL(fitness_prep_kernel, dim3(npairs), dim3(kPrepWG), 0, st, a, w, test);
-    return hipGetLastError();
-}
-
-hipError_t launch_finish(const PairArgs& a, const WorkArgs& w, int npairs, hipStream_t st) {
-    hipLaunchKernelGGL(finish_kernel, dim3(npairs), dim3(kFinWG), 0, st, a, w);
     return hipGetLastError();
 }
 
