@@ -53,7 +53,7 @@ __device__ __forceinline__ void mo_quant(const WorkArgs& w, int p, float* lo, fl
     }
 }
 
-// query records {index | sorted position << kNtPosShift, ...} and nn_t[i].w (nt_pack, icp4r_kernels.hip)
+// query records {index | sorted position << kNtPosShift, ...} and nn_t[i].w (nt_pack, icp4r_tile.hpp)
 constexpr int kNtPosShift = 14;
 constexpr int kNtIdxMask = (1 << kNtPosShift) - 1;
 

@@ -225,13 +225,15 @@ inline int64_t pass_tick_base(int npairs) { return 32 + 20 * (int64_t)npairs; }
 //   pruned / tile (single pairs, small batches, targets of any size; one stream)
 //     launch_init, launch_index
 //     per iteration:
-//       launch_nn_tile     [nn_seed_kernel] nn_tile_kernel [corr_kernel] — one tile: the search alone
-//         or launch_nn_pruned   [nn_seed_kernel] nn_pruned_kernel<Q, B> [corr_kernel]   (plan option nn_tile = 0)
+//       launch_nn_tile     [nn_seed_kernel] nn_tile_kernel [launch_corr] — one tile: the search alone
+//         or launch_nn_pruned   [nn_seed_kernel] nn_pruned_kernel<Q, B> [launch_corr]   (plan option nn_tile = 0)
 //       launch_update      fold_update_held_kernel / fold_update_wide_kernel (at most one pair per CU), else
 //                          fold_update_kernel; F64 numerics: update_f64_kernel
 //     [launch_fitness_prep], the search once more (fitness), launch_finish
 //     brute force (small targets, ICP4R_NN_BRUTE): launch_nn in the search's place, launch_update with
-//     need_corr (corr_kernel first), no launch_index
+//     need_corr (launch_corr first), no launch_index
+//     launch_corr        corr_kernel: the correspondence records from the merged keys, where the search did
+//                        not write them itself — called by launch_nn_tile, launch_nn_pruned and launch_update
 //
 //   solo (the tile plan's pairs when every target fits one LDS tile; sources <= kSoloMaxN by default)
 //     launch_init, launch_index, launch_solo          solo_kernel: every iteration, the fitness pass and the
@@ -256,9 +258,11 @@ hipError_t launch_index_cloud(const PairArgs& a, const WorkArgs& w, int npairs, 
 hipError_t launch_nn_pruned(int q, int chunk_sb, int chunks, const PairArgs& a, const WorkArgs& w, int npairs,
                             int max_n, int fitness_pass, int first, hipStream_t st);
 // the pruned plan's LDS-tiled search: nn_seed_kernel, nn_tile_kernel (target tiles x query parts),
-// corr_kernel (records, when the update reads them)
+// launch_corr (records, when the update reads them)
 hipError_t launch_nn_tile(const PairArgs& a, const WorkArgs& w, int npairs, int max_n, int max_m, int fitness_pass,
                           int first, int qrun, hipStream_t st, hipEvent_t tile_start = nullptr, hipEvent_t tile_stop = nullptr);
+// corr_kernel, its one launch: every active pair's correspondence records from its merged keys
+hipError_t launch_corr(const PairArgs& a, const WorkArgs& w, int npairs, int max_n, hipStream_t st);
 // events recorded around the batched NN's stages (any may be null)
 struct NNLdsEvents {
     hipEvent_t test_start = nullptr, test_stop = nullptr, search_start = nullptr, search_stop = nullptr;
