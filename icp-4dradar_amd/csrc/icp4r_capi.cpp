@@ -790,6 +790,8 @@ int icp4r_destroy(icp4r_ctx* ctx) {
     (void)hipStreamSynchronize(ctx->stream);
     for (icp4r_map* m : ctx->maps) icp4r_host::map_detach(m);
     ctx->maps.clear();
+    for (icp4r_voxel_acc* a : ctx->voxel_accs) icp4r_host::voxel_acc_detach(a);
+    ctx->voxel_accs.clear();
     for (int g = 0; g < kMaxGroups; ++g) {
         if (ctx->aux_stream[g]) (void)hipStreamDestroy(ctx->aux_stream[g]);
         if (ctx->fork_ev[g]) (void)hipEventDestroy(ctx->fork_ev[g]);

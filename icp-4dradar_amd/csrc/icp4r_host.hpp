@@ -96,6 +96,13 @@ void map_detach(icp4r_map* m);
 icp4r_ctx* map_context(const icp4r_map* m);
 }  // namespace icp4r_host
 
+struct icp4r_voxel_acc;
+namespace icp4r_host {
+// icp4r_destroy, as map_detach: frees the accumulator's device memory and leaves it detached — every
+// entry on it then fails with ICP4R_E_INVALID and icp4r_voxel_acc_destroy only deletes the host struct
+void voxel_acc_detach(icp4r_voxel_acc* a);
+}  // namespace icp4r_host
+
 struct icp4r_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -117,6 +124,8 @@ struct icp4r_ctx {
     // map stores created on this context (icp4r_map.cpp): registered by icp4r_map_create, removed by
     // icp4r_map_destroy, detached by icp4r_destroy — a map may outlive its context
     std::vector<icp4r_map*> maps;
+    // incremental voxel grids created on this context (icp4r_voxel_acc.cpp): the same lifetime rule
+    std::vector<icp4r_voxel_acc*> voxel_accs;
     // HIP events on the launch stream: the dominant NN kernel (the batched search, or the whole NN
     // launch of the other plans), the cache-test kernel, the update kernel, whole registrations
     std::vector<icp4r_host::EventPair> nn_events, test_events, upd_events, batch_events;

@@ -371,6 +371,57 @@ hipError_t launch_voxel_grid(const float4* pts, int64_t n, const VoxelArgs& a, v
 hipError_t launch_voxel_filter(const float4* pts, int64_t n, const VoxelArgs& a, int bits, void* work, float4* out,
                                int32_t* count, hipStream_t st);
 
+// ---- the incremental voxel grid (icp4r_voxel_acc.hip; include/icp4r/icp4r_voxel_acc.h)
+constexpr int kAccAxisBits = 21;                   // a cell's biased offset from the origin per axis
+constexpr int32_t kAccBias = 1 << (kAccAxisBits - 1);
+constexpr int kAccMergeBlock = 2048;               // state elements per workgroup of the merge kernel
+constexpr int kAccSmall = 8192;                    // scans of at most this many points: one workgroup sorts them in LDS
+// The accumulator's device-resident head: what every add folds and every filter reads.
+struct AccMeta {
+    uint32_t bbox[6];    // the accumulated box of the participating points (order-preserving words)
+    int32_t nvox;        // voxels in the current state buffer
+    int32_t origin[3];   // the cell all keys are relative to (valid with have_origin)
+    int32_t have_origin;
+    int32_t range;       // sticky: a device add left the range and was skipped
+    int32_t grid_flag;   // voxel_grid_from_bbox of bbox: 0 a grid, 1 no participating point, -1 overflow
+    int32_t pad;
+};
+// What the prep kernel leaves for the other kernels of one add (and the host entry reads back).
+struct AccScanInfo {
+    int32_t skip;        // 0: merge; 1: no participating point; 2: outside the range
+    int32_t minc[3];     // the scan's minimum cell
+    int32_t ext[3];      // cells per axis of the scan's own box
+    int32_t pad;
+    int64_t cells;       // ext0 ext1 ext2 (saturated): <= INT32_MAX lets one sort do
+};
+// One sorted state buffer: voxel v is (key[v], sums[v], count[v]), keys ascending.
+struct AccState {
+    uint64_t* key;       // (oz << 42) | (oy << 21) | ox, biased offsets
+    float4* sums;        // the four chains so far
+    uint32_t* count;     // members so far
+};
+struct AccLayout {  // byte offsets into the add workspace of a scan of n points
+    size_t bbox, info, tot, pkey, pa, pb, counts, offsets, skey, heads, posf, newrank, newkeys, bytes;
+};
+AccLayout acc_layout(int64_t n);
+hipError_t launch_acc_clear(AccMeta* meta, hipStream_t st);
+// Stage 1 of an add: the scan's box, the range rule, the fold into meta (sticky: a scan outside the
+// range sets meta->range — the device entry; the host entry reads info back and refuses instead).
+hipError_t launch_acc_prep(const float4* pts, int64_t n, const VoxelArgs& a, AccMeta* meta, void* work, int sticky,
+                           hipStream_t st);
+// Stage 2, after stage 1 on the same stream.  A scan of more than kAccSmall points is sorted by the
+// store's radix sort — sort_bits > 0: one sort of the scan-relative key's low sort_bits bits (info.cells
+// <= INT32_MAX); 0: two sorts of the 64-bit key's words.  max_vox: the
+// host's bound on meta->nvox before the add.  Merges cur into next (room for max_vox + n voxels).
+hipError_t launch_acc_merge(const float4* pts, int64_t n, const VoxelArgs& a, int sort_bits, AccMeta* meta,
+                            const AccState& cur, const AccState& next, int64_t max_vox, void* work, hipStream_t st);
+// The centroids of the state in key order to out (room for max_vox points) and their number to *count
+// (-1: grid overflow, -2: the range flag; nothing written then).  scan: acc_filter_scan_bytes(max_vox)
+// of block counts, offsets and one total, used when a.min_pts > 1.
+size_t acc_filter_scan_bytes(int64_t max_vox);
+hipError_t launch_acc_filter(const AccMeta* meta, const AccState& cur, int64_t max_vox, const VoxelArgs& a,
+                             int32_t* scan, float4* out, int32_t* count, hipStream_t st);
+
 // ---- the map's k-NN index and search (icp4r_map_knn.hip)
 // A snapshot of the first `indexed` stored points: their float4 copy in Morton order (.w = the bits of
 // the insertion position; a point with a non-finite coordinate, and the padding up to a whole leaf,

@@ -92,6 +92,12 @@ VOXEL_EXPORTED_SYMBOLS = [
     "icp4r_voxel_params_default", "icp4r_voxel_filter", "icp4r_voxel_filter_device", "icp4r_map_voxel_filter",
     "icp4r_map_voxel_filter_device", "icp4r_voxel_time_ms", "icp4r_voxel_time_reset",
 ]
+# include/icp4r/icp4r_voxel_acc.h (the incremental voxel grid; icp4r.voxel.VoxelAccumulator)
+VOXEL_ACC_EXPORTED_SYMBOLS = [
+    "icp4r_voxel_acc_create", "icp4r_voxel_acc_destroy", "icp4r_voxel_acc_clear", "icp4r_voxel_acc_reserve",
+    "icp4r_voxel_acc_add", "icp4r_voxel_acc_add_device", "icp4r_voxel_acc_add_map", "icp4r_voxel_acc_filter",
+    "icp4r_voxel_acc_filter_device", "icp4r_voxel_acc_size",
+]
 
 
 def status_name(code: int) -> str:
@@ -234,6 +240,17 @@ def load():
         "icp4r_map_voxel_filter_device": (C.c_int, [vp, vp, vp, vp, vp]),
         "icp4r_voxel_time_ms": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(i32)]),
         "icp4r_voxel_time_reset": (C.c_int, [vp]),
+        # icp4r_voxel_acc.h
+        "icp4r_voxel_acc_create": (C.c_int, [vp, vp, C.POINTER(vp)]),
+        "icp4r_voxel_acc_destroy": (C.c_int, [vp]),
+        "icp4r_voxel_acc_clear": (C.c_int, [vp]),
+        "icp4r_voxel_acc_reserve": (C.c_int, [vp, i64]),
+        "icp4r_voxel_acc_add": (C.c_int, [vp, vp, i64, i32]),
+        "icp4r_voxel_acc_add_device": (C.c_int, [vp, vp, i64, vp]),
+        "icp4r_voxel_acc_add_map": (C.c_int, [vp, vp]),
+        "icp4r_voxel_acc_filter": (C.c_int, [vp, vp, i64, C.POINTER(i64)]),
+        "icp4r_voxel_acc_filter_device": (C.c_int, [vp, vp, vp, vp]),
+        "icp4r_voxel_acc_size": (C.c_int, [vp, C.POINTER(i64), C.POINTER(i64)]),
         # icp4r_multi.h
         "icp4r_shard": (C.c_int, [i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]),
         "icp4r_align_batch_multi": (C.c_int, [C.POINTER(vp), i32, vp, vp, vp, vp, vp, vp, i32, vp, C.POINTER(Params),

@@ -8,7 +8,8 @@ reference's radar_odometry node uses it for its surround map (radar_odometry.cpp
 
 Same method names; clouds are (N, >=3) float32 arrays (x, y, z[, intensity]), the result is (K, 4)
 float32 in ascending leaf index.  GPU-only: there is no CPU fallback.  A map that is already resident
-filters itself: KD_TREE.voxel_filter / voxel_filter_device (icp4r.mapstore).
+filters itself: KD_TREE.voxel_filter / voxel_filter_device (icp4r.mapstore).  VoxelAccumulator is the
+incremental form (include/icp4r/icp4r_voxel_acc.h): add each scan once, then filter.
 """
 from __future__ import annotations
 
@@ -99,3 +100,86 @@ class VoxelGrid:
 
     def reset_timers(self):
         _check(self._lib.icp4r_voxel_time_reset(self._ctx.handle), "icp4r_voxel_time_reset")
+
+
+class VoxelAccumulator:
+    """The incremental voxel grid (include/icp4r/icp4r_voxel_acc.h): hand over each scan once, get the
+    downsampled map back.  After any sequence of adds, filter() equals VoxelGrid.filter of the
+    concatenation of all added clouds, bit for bit.  The parameters are fixed for the accumulator's life."""
+
+    def __init__(self, leaf, downsample_all_data: bool = True, min_points_per_voxel: int = 0, ctx: Context | None = None):
+        self._ctx = ctx or default_context()
+        self._lib = load()
+        self._p = voxel_params(leaf, downsample_all_data, min_points_per_voxel)
+        self._h = C.c_void_p()
+        _check(self._lib.icp4r_voxel_acc_create(self._ctx.handle, C.byref(self._p), C.byref(self._h)),
+               "icp4r_voxel_acc_create")
+
+    def close(self):
+        if self._h:
+            self._lib.icp4r_voxel_acc_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def params(self) -> VoxelParams:
+        return self._p
+
+    def add(self, cloud):
+        """One scan, (N, >=3) float32.  Raises ICP4RError (ICP4R_E_TOO_LARGE) when the scan leaves the
+        range of +-2^20 cells around the origin; the accumulator is then as it was."""
+        a, n, stride = _cloud(cloud)
+        _check(self._lib.icp4r_voxel_acc_add(self._h, _ptr(a), n, stride), "icp4r_voxel_acc_add")
+
+    def add_device(self, d_points: int, n: int, stream=None):
+        """n float4 points at device address d_points, asynchronously on stream.  A scan outside the range
+        is skipped whole and makes filter_device store -2 (filter raise) until clear()."""
+        vp = lambda x: C.c_void_p(x) if x else None  # noqa: E731
+        _check(self._lib.icp4r_voxel_acc_add_device(self._h, vp(d_points), int(n), vp(stream)), "icp4r_voxel_acc_add_device")
+
+    def add_map(self, tree):
+        """The points of a map store (icp4r.mapstore.KD_TREE) of the same context, as one add."""
+        _check(self._lib.icp4r_voxel_acc_add_map(self._h, tree.handle), "icp4r_voxel_acc_add_map")
+
+    def size(self) -> tuple[int, int]:
+        """(stored voxels, points added)."""
+        v, p = C.c_int64(), C.c_int64()
+        _check(self._lib.icp4r_voxel_acc_size(self._h, C.byref(v), C.byref(p)), "icp4r_voxel_acc_size")
+        return v.value, p.value
+
+    def filter(self) -> np.ndarray:
+        """The voxel centroids, (K, 4) float32, in ascending leaf index.  Raises ICP4RError
+        (ICP4R_E_TOO_LARGE) on grid overflow and after a device add that left the range."""
+        cap = self.size()[0]
+        out = np.empty((max(cap, 1), 4), np.float32)
+        k = C.c_int64()
+        _check(self._lib.icp4r_voxel_acc_filter(self._h, _ptr(out), cap, C.byref(k)), "icp4r_voxel_acc_filter")
+        return out[:k.value].copy()
+
+    def filter_device(self, d_out: int, d_count: int, stream=None):
+        """The centroids (float4, room for size()[0]) to d_out and their int32 count to d_count (-1: grid
+        overflow, -2: a device add left the range), asynchronously on stream."""
+        vp = lambda x: C.c_void_p(x) if x else None  # noqa: E731
+        _check(self._lib.icp4r_voxel_acc_filter_device(self._h, vp(d_out), vp(d_count), vp(stream)),
+               "icp4r_voxel_acc_filter_device")
+
+    def clear(self):
+        _check(self._lib.icp4r_voxel_acc_clear(self._h), "icp4r_voxel_acc_clear")
+
+    def reserve(self, voxels: int):
+        _check(self._lib.icp4r_voxel_acc_reserve(self._h, int(voxels)), "icp4r_voxel_acc_reserve")
