@@ -49,8 +49,11 @@ int opt(const icp4r_ctx* ctx, PlanOpt k, int dflt);
 // caller whose index strides exceed what it stages, icp4r_gicp.cpp), so every other field of the
 // plan is the one of the plan that runs.
 // registration = true: the plan of run_pairs for PCL numerics (solo_kernel where it applies).
+// reciprocal = true: the plan of a registration with use_reciprocal_correspondences — no solo_kernel and
+// no cached-neighbour test (the reciprocal stage sits between the search and the update, and marks a
+// rejection in the keys and records those forms do not keep), whatever the plan options say.
 Plan make_plan(const icp4r_ctx* ctx, int npairs, int max_n, int max_m, int nn_mode = ICP4R_NN_AUTO,
-               bool allow_lds = true, bool registration = false);
+               bool allow_lds = true, bool registration = false, bool reciprocal = false);
 // icp4r_params -> the kernels' KParams (validates).
 int make_kparams(const icp4r_params* p, icp4r::KParams* kp);
 // Size the context's workspace for a plan and fill WorkArgs.

@@ -120,7 +120,7 @@ int opt(const icp4r_ctx* ctx, PlanOpt k, int dflt) {
 //    keeps >= 256 targets.  Q = 4 scalar measured fastest (tools/experiments/tune_sweep.py, profiles/tune_r01.jsonl).
 // Tuning overrides (tools/experiments/tune_sweep.py): ICP4R_NN_Q caps Q, ICP4R_LEAF = 16 | 32.
 Plan make_plan(const icp4r_ctx* ctx, int npairs, int max_n, int max_m, int nn_mode, bool allow_lds,
-               bool registration) {
+               bool registration, bool reciprocal) {
     Plan pl;
     pl.pruned = nn_mode == ICP4R_NN_PRUNED || (nn_mode == ICP4R_NN_AUTO && max_m >= kPrunedMinM);
     pl.packed = false;
@@ -166,7 +166,7 @@ Plan make_plan(const icp4r_ctx* ctx, int npairs, int max_n, int max_m, int nn_mo
             pl.q = 2;
             pl.blocks = npairs;
             pl.chunks = 1;
-            pl.cache = opt(ctx, kOptNnCache, 1) != 0;
+            pl.cache = !reciprocal && opt(ctx, kOptNnCache, 1) != 0;
         } else {
             // single pairs / small batches: the LDS-tiled search (target tiles of 8192 x query parts)
             pl.tile = pl.leaf == 16 && max_m < (1 << 19) && opt(ctx, kOptNnTile, 1) != 0;
@@ -194,7 +194,7 @@ Plan make_plan(const icp4r_ctx* ctx, int npairs, int max_n, int max_m, int nn_mo
             // tools/experiments/solo_sweep.py, profiles/round3/s4/solo_sweep_r16.jsonl; plan option solo = 1 forces it up to
             // kCacheMaxN, 0 disables it)
             const int solo_env = opt(ctx, kOptSolo, -1);
-            pl.solo = registration && pl.tile && pl.chunks == 1 && solo_env != 0 &&
+            pl.solo = registration && !reciprocal && pl.tile && pl.chunks == 1 && solo_env != 0 &&
                       max_n <= (solo_env == 1 ? kCacheMaxN : kSoloMaxN);
             if (pl.solo) pl.blocks = npairs;
         }
@@ -230,6 +230,9 @@ int make_kparams(const icp4r_params* p, KParams* kp) {
         p->nn_mode != ICP4R_NN_PRUNED)
         return fail(ICP4R_E_INVALID, "unknown nn_mode %d", p->nn_mode);
     if (!(p->huber_delta > 0)) return fail(ICP4R_E_INVALID, "huber_delta must be > 0 (+inf disables)");
+    if (p->use_reciprocal_correspondences != 0 && p->use_reciprocal_correspondences != 1)
+        return fail(ICP4R_E_INVALID, "use_reciprocal_correspondences must be 0 or 1 (got %d)",
+                    p->use_reciprocal_correspondences);
     memset(kp, 0, sizeof(*kp));
     kp->conv.max_iterations = p->max_iterations;
     kp->conv.max_similar = p->max_iterations_similar_transforms;
@@ -495,15 +498,32 @@ void group_view(const PairArgs& a, const WorkArgs& w, int p0, int g, PairArgs& a
 // Large batched (LDS-plan) batches run as `groups` independent pair groups on their own streams,
 // forked from and joined back into `st`: a group's HBM-bound kernels (cache test, fold) overlap the
 // latency/issue-bound search of another (ICP4R_GROUPS, default kDefaultGroups).
+// recip (icp4r_params.use_reciprocal_correspondences): launch_recip between the search and the update
+// of every iteration, on a plan whose update reads the keys and records the stage marks — no solo_kernel,
+// no cached-neighbour test (make_plan), hence no fused tail, work list, on-chip or lazy update, and the
+// records formed by the search or corr_kernel (no fold_keys).
 int run_pairs(icp4r_ctx* ctx, const PairArgs& a, int npairs, int max_n, int max_m, int max_iterations,
-              int nn_mode, hipStream_t st) {
+              int nn_mode, bool recip, hipStream_t st) {
     if (npairs <= 0) return ICP4R_OK;
     const int mn = max_n > 0 ? max_n : 1;
     const bool pcl = a.kp.numerics == kNumericsPCL;
-    const Plan pl = make_plan(ctx, npairs, mn, max_m, nn_mode, true, pcl);
+    const Plan pl = make_plan(ctx, npairs, mn, max_m, nn_mode, true, pcl, recip);
     WorkArgs w;
     int rc;
     if ((rc = setup_work(ctx, pl, npairs, max_n, max_m, pcl && !pl.solo, st, w))) return rc;
+    RecipArgs rw;
+    memset(&rw, 0, sizeof(rw));
+    if (recip) {
+        rw.w_stride = max_m > 0 ? max_m : 1;
+        rw.s_stride = ((int64_t)mn + 255) / 256 * 256;
+        rw.b_stride = rw.s_stride / kRecipLeaf;
+        HIP_TRY(ctx->recip_win.ensure((size_t)npairs * 2 * rw.w_stride * sizeof(NNKey)));
+        HIP_TRY(ctx->recip_src.ensure((size_t)npairs * rw.s_stride * sizeof(float4)));
+        HIP_TRY(ctx->recip_box.ensure((size_t)npairs * 2 * rw.b_stride * sizeof(float4)));
+        rw.win = static_cast<NNKey*>(ctx->recip_win.p);
+        rw.rsrc = static_cast<float4*>(ctx->recip_src.p);
+        rw.rbox = static_cast<float4*>(ctx->recip_box.p);
+    }
     // sources ordered by their target's kd tree (src_order_kernel) on the batched plan, where its
     // better first-pass seeds and one kd build per pair pay (C3 +2.9 %); a single pair's extra launch
     // does not (C1 0.75 -> 0.80 ms), so the unbatched plans build the source's own tree
@@ -514,6 +534,7 @@ int run_pairs(icp4r_ctx* ctx, const PairArgs& a, int npairs, int max_n, int max_
     w.seed_next = (pl.tile && pl.chunks > 1 && pcl && w.corr && opt(ctx, kOptFuseSeed, 1) != 0) ? 1 : 0;
     // one-tile plan (C1, C2), PCL numerics: the update's transformCloud(T_inc) deferred into the next
     // search, which reads every query anyway (nn_tile_kernel; plan option tile_defer = 0: the update does it)
+    // (a reciprocal registration too: the search stores the moved X before the stage reads it)
     if (pl.tile && pl.chunks == 1 && !pl.solo && pcl && w.corr && opt(ctx, kOptTileOwn, 1) != 0 &&
         opt(ctx, kOptTileDefer, 1) != 0)
         w.defer_xform = 1;
@@ -563,9 +584,18 @@ int run_pairs(icp4r_ctx* ctx, const PairArgs& a, int npairs, int max_n, int max_
     // each 91.5k pairs/s, on 256 CUs each 89.5k, one group 88.4k — measured in one session)
     const int cdiv = opt(ctx, kOptSearchCuDiv, groups);
     const int search_cu = cdiv > 1 ? (ctx->ncu + cdiv - 1) / cdiv : 0;
+    RecipArgs rg[kMaxGroups];
     for (int g = 0; g < groups; ++g) {
         HIP_TRY(launch_init(ag[g], wg[g], gn[g], gs[g]));
         if (pl.pruned) HIP_TRY(launch_index(ag[g], wg[g], gn[g], gs[g]));
+        rg[g] = rw;
+        if (recip) {  // the group's slice of the stage's workspace; both winner buffers start all-ones
+            const int64_t p0 = (int64_t)npairs * g / groups;
+            rg[g].win += p0 * 2 * rw.w_stride;
+            rg[g].rsrc += p0 * rw.s_stride;
+            rg[g].rbox += p0 * 2 * rw.b_stride;
+            HIP_TRY(hipMemsetAsync(rg[g].win, 0xFF, (size_t)gn[g] * 2 * rw.w_stride * sizeof(NNKey), gs[g]));
+        }
     }
     // PCL's do { ... } while (!converged): at least one iteration even for max_iterations == 0.
     const int iters = max_iterations > 0 ? max_iterations : 1;
@@ -606,10 +636,14 @@ int run_pairs(icp4r_ctx* ctx, const PairArgs& a, int npairs, int max_n, int max_
     // ... with the records held in registers from pass A to pass B for sources of at most kHeldMaxN
     // points (fold_update_held_kernel; plan option held_update = 0: fold_update_wide_kernel)
     for (int g = 0; g < groups; ++g)
-        wg[g].held_update = (wide && mn <= kHeldMaxN && opt(ctx, kOptHeldUpdate, kDefaultHeldUpdate) != 0) ? 1 : 0;
+        // (not a reciprocal registration's: the held form re-evaluates d² from the record's two points and
+        // would not see the reciprocal stage's mark; the wide form reads the record's d²)
+        wg[g].held_update =
+            (wide && !recip && mn <= kHeldMaxN && opt(ctx, kOptHeldUpdate, kDefaultHeldUpdate) != 0) ? 1 : 0;
     // ... which, on the multi-tile plan (the scan-to-map target), forms the correspondence records in
     // its pass A instead of corr_kernel after every search (plan option fold_keys = 0: corr_kernel)
-    if (wide && pl.tile && !pl.lds && w.corr && (pl.chunks > 1 || !w.tile_own) && opt(ctx, kOptFoldKeys, 1) != 0)
+    if (wide && !recip && pl.tile && !pl.lds && w.corr && (pl.chunks > 1 || !w.tile_own) &&
+        opt(ctx, kOptFoldKeys, 1) != 0)
         for (int g = 0; g < groups; ++g) wg[g].fold_keys = 1;
     char pass_name[48];
     for (int it = 0; it < iters; ++it) {
@@ -620,12 +654,23 @@ int run_pairs(icp4r_ctx* ctx, const PairArgs& a, int npairs, int max_n, int max_
             if ((rc = nn_pass(ctx, pl, ag[g], wg[g], gn[g], mn, 0, it == 0, gs[g], search_cu, fuse && it > 0, it,
                               ford && it > 0, silent_tail(it - 1) ? 1 : 0)))
                 return rc;
+            // brute force, PCL numerics: the records come from the keys (corr_kernel) — after the stage's marks
+            bool need_corr = pcl && !pl.pruned;
+            if (recip) {
+                EventPair* re = nullptr;
+                if (kev) {
+                    if ((rc = next_event(ctx->recip_events, ctx->recip_used, &re))) return rc;
+                    HIP_TRY(hipEventRecord(re->start, gs[g]));
+                }
+                HIP_TRY(launch_recip(ag[g], wg[g], rg[g], gn[g], mn, it & 1, gs[g]));
+                if (kev) HIP_TRY(hipEventRecord(re->stop, gs[g]));
+            }
             EventPair* ue = nullptr;
             if (kev) {
                 if ((rc = next_event(ctx->upd_events, ctx->upd_used, &ue))) return rc;
                 HIP_TRY(hipEventRecord(ue->start, gs[g]));
             }
-            HIP_TRY(launch_update(ag[g], wg[g], gn[g], mn, pcl && !pl.pruned, gs[g], fuse && it + 1 < iters,
+            HIP_TRY(launch_update(ag[g], wg[g], gn[g], mn, need_corr, gs[g], fuse && it + 1 < iters,
                                   ford && it + 1 < iters ? ncu_g : 0, wide, silent_tail(it) ? 1 : 0,
                                   silent_tail(it - 1) ? 1 : 0));
             if (kev) HIP_TRY(hipEventRecord(ue->stop, gs[g]));
@@ -799,13 +844,14 @@ int icp4r_destroy(icp4r_ctx* ctx) {
     for (DevBuf* b : {&ctx->src, &ctx->tgt, &ctx->src_off, &ctx->src_n, &ctx->tgt_off, &ctx->tgt_n, &ctx->guess,
                       &ctx->aligned, &ctx->results, &ctx->T, &ctx->X, &ctx->nn_key,
                       &ctx->state, &ctx->tsort, &ctx->tinv, &ctx->tbox, &ctx->sbox, &ctx->sperm, &ctx->evals, &ctx->corr, &ctx->ticks, &ctx->nn_lu, &ctx->nn_t, &ctx->kdn, &ctx->sq, &ctx->sm, &ctx->qv, &ctx->qm, &ctx->need,
-                      &ctx->miss_cnt, &ctx->plist, &ctx->plist_n, &ctx->owork, &ctx->ego_rec, &ctx->ego_off, &ctx->ego_cnt, &ctx->ego_feat,
+                      &ctx->miss_cnt, &ctx->plist, &ctx->plist_n, &ctx->owork, &ctx->recip_win, &ctx->recip_src, &ctx->recip_box, &ctx->ego_rec, &ctx->ego_off, &ctx->ego_cnt, &ctx->ego_feat,
                       &ctx->ego_pd, &ctx->ego_scores, &ctx->ego_res, &ctx->ego_mask, &ctx->ego_xyzi, &ctx->gicp_gs,
                       &ctx->gicp_cov_src, &ctx->gicp_cov_tgt, &ctx->gicp_mah, &ctx->gicp_active, &ctx->gicp_part, &ctx->gicp_sidx, &ctx->vox_work,
                       &ctx->vox_in, &ctx->vox_out, &ctx->vox_cnt, &ctx->gate_counts, &ctx->gate_base, &ctx->gate_cnt,
                       &ctx->gate_bad, &ctx->gate_mask, &ctx->gate_clouds, &ctx->gate_pair_off, &ctx->gate_pair_n})
         b->release();
-    for (auto* v : {&ctx->nn_events, &ctx->test_events, &ctx->upd_events, &ctx->batch_events, &ctx->gicp_events, &ctx->vox_events})
+    for (auto* v : {&ctx->nn_events, &ctx->test_events, &ctx->upd_events, &ctx->batch_events, &ctx->recip_events,
+                    &ctx->gicp_events, &ctx->vox_events})
         for (auto& ev : *v) {
             (void)hipEventDestroy(ev.start);
             (void)hipEventDestroy(ev.stop);
@@ -864,7 +910,9 @@ int icp4r_align(icp4r_ctx* ctx, const float* src, int32_t n, int32_t src_stride_
     a.results = static_cast<Result*>(ctx->results.p);
     a.kp = kp;
     const int iters = params ? params->max_iterations : 10;
-    if ((rc = run_pairs(ctx, a, 1, n, m, iters, params ? params->nn_mode : ICP4R_NN_AUTO, st))) return rc;
+    if ((rc = run_pairs(ctx, a, 1, n, m, iters, params ? params->nn_mode : ICP4R_NN_AUTO,
+                        params && params->use_reciprocal_correspondences != 0, st)))
+        return rc;
     HIP_TRY(hipMemcpyAsync(out, ctx->results.p, sizeof(icp4r_result), hipMemcpyDeviceToHost, st));
     std::vector<float> ha;
     if (aligned_out && n > 0) {
@@ -921,7 +969,7 @@ int icp4r_align_batch_device(icp4r_ctx* ctx, const icp4r_batch* b, const icp4r_p
     a.kp = kp;
     hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->stream;
     return run_pairs(ctx, a, b->npairs, b->max_src_n, b->max_tgt_n, params ? params->max_iterations : 10,
-                     params ? params->nn_mode : ICP4R_NN_AUTO, st);
+                     params ? params->nn_mode : ICP4R_NN_AUTO, params && params->use_reciprocal_correspondences != 0, st);
 }
 
 int icp4r_align_batch_host(icp4r_ctx* ctx, const float* src, const int64_t* src_off, const int32_t* src_n,
@@ -931,6 +979,11 @@ int icp4r_align_batch_host(icp4r_ctx* ctx, const float* src, const int64_t* src_
     icp4r_host::Range range("icp4r_align_batch_host");
     if (npairs == 0) return ICP4R_OK;
     if (!src_off || !src_n || !tgt_off || !tgt_n) return fail(ICP4R_E_INVALID, "NULL offset/count array");
+    {  // the parameters are refused before any device call, as icp4r_align does
+        KParams kp;
+        const int prc = make_kparams(params, &kp);
+        if (prc) return prc;
+    }
     // only the point ranges the pairs cover are uploaded, offsets rebased to them (a shard of a larger
     // host batch, icp4r_align_batch_multi, uploads its own points only)
     int64_t s_lo = INT64_MAX, s_hi = 0, t_lo = INT64_MAX, t_hi = 0;
@@ -1071,6 +1124,7 @@ int icp4r_stage_time_ms(icp4r_ctx* ctx, int32_t stage, double* avg_ms, int32_t* 
         case ICP4R_STAGE_UPDATE: v = &ctx->upd_events; used = ctx->upd_used; break;
         case ICP4R_STAGE_BATCH: v = &ctx->batch_events; used = ctx->batch_used; break;
         case ICP4R_STAGE_GICP_COV: v = &ctx->gicp_events; used = ctx->gicp_used; break;
+        case ICP4R_STAGE_RECIPROCAL: v = &ctx->recip_events; used = ctx->recip_used; break;
         default: return fail(ICP4R_E_INVALID, "unknown stage %d", stage);
     }
     HIP_TRY(hipSetDevice(ctx->device));
@@ -1092,6 +1146,7 @@ int icp4r_kernel_time_reset(icp4r_ctx* ctx) {
     ctx->upd_used = 0;
     ctx->batch_used = 0;
     ctx->gicp_used = 0;
+    ctx->recip_used = 0;
     if (ctx->evals.p) {
         HIP_TRY(hipSetDevice(ctx->device));
         HIP_TRY(hipDeviceSynchronize());

@@ -114,6 +114,7 @@ struct icp4r_ctx {
     // batch workspace
     icp4r_host::DevBuf X, nn_key, state, tsort, tinv, tbox, sbox, sperm, corr, ticks, nn_lu, nn_t, kdn, sq, sm, qv, qm, need,
         miss_cnt, plist, plist_n, owork, mo_hist, mo_rep;  // nn_lu holds U (float) per source point
+    icp4r_host::DevBuf recip_win, recip_src, recip_box;  // the reciprocal stage's workspace (icp4r::RecipArgs)
     int ncu = 256;  // compute units of the device (persistent launches)
     bool kernel_timing = false;  // per-kernel events (icp4r_set_kernel_timing)
     // plan options (icp4r_set_plan_option; icp4r_pipe::PlanOpt): values, and which are set
@@ -128,8 +129,8 @@ struct icp4r_ctx {
     std::vector<icp4r_voxel_acc*> voxel_accs;
     // HIP events on the launch stream: the dominant NN kernel (the batched search, or the whole NN
     // launch of the other plans), the cache-test kernel, the update kernel, whole registrations
-    std::vector<icp4r_host::EventPair> nn_events, test_events, upd_events, batch_events;
-    size_t nn_used = 0, test_used = 0, upd_used = 0, batch_used = 0;
+    std::vector<icp4r_host::EventPair> nn_events, test_events, upd_events, batch_events, recip_events;
+    size_t nn_used = 0, test_used = 0, upd_used = 0, batch_used = 0, recip_used = 0;
     icp4r_host::DevBuf evals;  // per-wave counter slots (kCountSlots x kCountStride u64), summed by the host
     // radar ego velocity (icp4r_ego.cpp): staging and workspace
     icp4r_host::DevBuf ego_rec, ego_off, ego_cnt, ego_feat, ego_pd, ego_scores, ego_res, ego_mask, ego_xyzi;

@@ -235,6 +235,10 @@ inline int64_t pass_tick_base(int npairs) { return 32 + 20 * (int64_t)npairs; }
 //     launch_corr        corr_kernel: the correspondence records from the merged keys, where the search did
 //                        not write them itself — called by launch_nn_tile, launch_nn_pruned and launch_update
 //
+//   reciprocal registrations (use_reciprocal_correspondences): launch_recip (icp4r_recip.hip) between the
+//     search and the update of every iteration, on the batched plan without the cached-neighbour test or
+//     the pruned / tile plan without fold_keys and the held update; never solo
+//
 //   solo (the tile plan's pairs when every target fits one LDS tile; sources <= kSoloMaxN by default)
 //     launch_init, launch_index, launch_solo          solo_kernel: every iteration, the fitness pass and the
 //                                                     result row of a pair by one workgroup in one launch
@@ -296,6 +300,24 @@ hipError_t launch_solo(const PairArgs& a, const WorkArgs& w, int npairs, int max
 hipError_t launch_fitness_prep(const PairArgs& a, const WorkArgs& w, int npairs, hipStream_t st, int test = 0);
 hipError_t launch_finish(const PairArgs& a, const WorkArgs& w, int npairs, hipStream_t st);
 hipError_t launch_rot_f32(const float* sigma, float* R, int k, hipStream_t st);
+
+// ---- reciprocal correspondences (icp4r_recip.hip; icp4r_params.use_reciprocal_correspondences)
+// The stage's own workspace, pair p at [p * stride, ...) of each array (run_pairs offsets a pair group's view).
+constexpr int kRecipLeaf = 64;  // sources per block of the reverse search (one wave's box)
+struct RecipArgs {
+    NNKey* win;        // [npairs * 2 * w_stride] per target: the smallest (d², source index) key that chose it,
+                       // two buffers taken in turn by parity (the vote clears the other one)
+    float4* rsrc;      // [npairs * s_stride] the moved source in index order (sperm), .w = original index bits
+    float4* rbox;      // [npairs * 2 * b_stride] per block of kRecipLeaf sorted sources: lo, hi
+    int64_t w_stride;  // >= max target points per pair
+    int64_t s_stride;  // max source points per pair rounded up to whole workgroups (256)
+    int64_t b_stride;  // s_stride / kRecipLeaf
+};
+// One iteration's reciprocal stage for every active pair, after the search and before the update: a
+// source whose nearest target has a nearer source (key order) gets d² = +inf in its key and record.
+// parity: the iteration's winner buffer (0 / 1 in turn; both all-ones before the first iteration).
+hipError_t launch_recip(const PairArgs& a, const WorkArgs& w, const RecipArgs& r, int npairs, int max_n, int parity,
+                        hipStream_t st);
 
 // ---- scan-to-map store (icp4r_map.hip)
 struct SectorArgs {

@@ -138,7 +138,7 @@ struct FrameOut {
 
 int usage() {
     std::fprintf(stderr, "usage: icp4radar_replay <dataset_folder> [--csv PATH] [--batch] [--devices D0,D1,...] [--seed S] "
-                         "[--max-iterations N] [--use-icp-result CSV] [--static-points]\n");
+                         "[--max-iterations N] [--reciprocal] [--use-icp-result CSV] [--static-points]\n");
     return 2;
 }
 
@@ -155,6 +155,7 @@ int main(int argc, char** argv) {
     icp4r_ego_params ep;
     icp4r_ego_params_default(&ep);
     int max_iterations = -1;  // PCL default (10) unless given
+    bool reciprocal = false;  // --reciprocal: setUseReciprocalCorrespondences(true) on every registration
     std::string icp_result_csv;
     for (int i = 2; i < argc; ++i) {
         if (!std::strcmp(argv[i], "--csv") && i + 1 < argc) csv = argv[++i];
@@ -170,6 +171,7 @@ int main(int argc, char** argv) {
         }
         else if (!std::strcmp(argv[i], "--seed") && i + 1 < argc) ep.seed = std::strtoull(argv[++i], nullptr, 0);
         else if (!std::strcmp(argv[i], "--max-iterations") && i + 1 < argc) max_iterations = std::atoi(argv[++i]);
+        else if (!std::strcmp(argv[i], "--reciprocal")) reciprocal = true;
         else if (!std::strcmp(argv[i], "--use-icp-result") && i + 1 < argc) icp_result_csv = argv[++i];
         else if (!std::strcmp(argv[i], "--static-points")) static_points = true;
         else return usage();
@@ -207,6 +209,7 @@ int main(int argc, char** argv) {
     icp4r_params ip;
     icp4r_params_default(&ip);
     if (max_iterations >= 0) ip.max_iterations = max_iterations;
+    ip.use_reciprocal_correspondences = reciprocal ? 1 : 0;
 
     // --static-points: the points each scan pushes onto the running clouds (float4), else its records
     std::vector<std::vector<float>> gated(static_points ? nframes : 0);
@@ -378,6 +381,7 @@ int main(int argc, char** argv) {
             icp.setInputSource(cloud_src_in);
             icp.setInputTarget(cloud_tar_in);
             if (max_iterations >= 0) icp.setMaximumIterations(max_iterations);
+            icp.setUseReciprocalCorrespondences(reciprocal);
             icp.align(Final);
             const double score = icp.getFitnessScore();
             const Eigen::Matrix4d icp_result = icp.getFinalTransformation().cast<double>();

@@ -35,7 +35,7 @@ OK, E_INVALID, E_EMPTY, E_TOO_FEW_CORR, E_NONFINITE, E_HIP, E_RCCL, E_NOMEM, E_T
 NUMERICS_PCL, NUMERICS_F64 = 0, 1
 NO_DEVICE = -1  # icp4r_create(&ctx, ICP4R_NO_DEVICE): plan queries and plan options only
 NN_AUTO, NN_BRUTE, NN_BRUTE_PACKED, NN_PRUNED = 0, 1, 2, 3
-STAGE_NN, STAGE_NN_TEST, STAGE_UPDATE, STAGE_BATCH, STAGE_GICP_COV = 0, 1, 2, 3, 4
+STAGE_NN, STAGE_NN_TEST, STAGE_UPDATE, STAGE_BATCH, STAGE_GICP_COV, STAGE_RECIPROCAL = 0, 1, 2, 3, 4, 5
 DBL_MAX = sys.float_info.max
 
 _STATUS = {OK: "ICP4R_OK", E_INVALID: "ICP4R_E_INVALID", E_EMPTY: "ICP4R_E_EMPTY",
@@ -127,7 +127,8 @@ class Params(C.Structure):
         ("fitness_max_range", C.c_double),
         ("eigen_l1_bytes", C.c_int32),
         ("eigen_gebp_mr", C.c_int32),
-        ("reserved", C.c_int32 * 6),
+        ("use_reciprocal_correspondences", C.c_int32),
+        ("reserved", C.c_int32 * 5),
     ]
 
 
@@ -418,7 +419,8 @@ class Context:
         _check(self._lib.icp4r_reset_plan_options(self._h), "icp4r_reset_plan_options")
 
     def stage_time_ms(self, stage: int) -> tuple[float, int]:
-        """(average ms, launches) of a stage (STAGE_NN, STAGE_NN_TEST, STAGE_UPDATE, STAGE_BATCH)."""
+        """(average ms, launches) of a stage (STAGE_NN, STAGE_NN_TEST, STAGE_UPDATE, STAGE_BATCH,
+        STAGE_RECIPROCAL)."""
         ms, k = C.c_double(), C.c_int32()
         _check(self._lib.icp4r_stage_time_ms(self._h, stage, C.byref(ms), C.byref(k)), "icp4r_stage_time_ms")
         return ms.value, k.value
@@ -523,6 +525,12 @@ class IterativeClosestPoint:
 
     def setEuclideanFitnessEpsilon(self, epsilon: float):
         self._p.euclidean_fitness_epsilon = float(epsilon)
+
+    def setUseReciprocalCorrespondences(self, use_reciprocal_correspondence: bool):
+        self._p.use_reciprocal_correspondences = 1 if use_reciprocal_correspondence else 0
+
+    def getUseReciprocalCorrespondences(self) -> bool:
+        return bool(self._p.use_reciprocal_correspondences)
 
     # build extensions (no PCL counterpart)
     def setHuberDelta(self, delta: float):

@@ -97,7 +97,12 @@ typedef struct icp4r_params {
      * coefficient (lazyproduct, an alignment-dependent vectorised redux); the GEMM panel form above is
      * used for every |C|.  Both host facts are assumptions about the node's build: parity with PCL
      * itself is unpinned (the reference holds no fixtures).                            */
-    int32_t reserved[6];
+    /* setUseReciprocalCorrespondences (PCL default false): 1 keeps a correspondence (i, m) only if the
+     * nearest neighbour of target m in the moved source is i again (determineReciprocalCorrespondences;
+     * same distance, ties to the lowest index).  The update, |C| < min_correspondences, the MSE and
+     * n_correspondences see the kept list; getFitnessScore is not reciprocal.  0 or 1.              */
+    int32_t use_reciprocal_correspondences;
+    int32_t reserved[5];
 } icp4r_params;
 
 typedef struct icp4r_result {
@@ -201,7 +206,8 @@ typedef enum icp4r_stage {
     ICP4R_STAGE_NN_TEST = 1,
     ICP4R_STAGE_UPDATE = 2,
     ICP4R_STAGE_BATCH = 3,
-    ICP4R_STAGE_GICP_COV = 4
+    ICP4R_STAGE_GICP_COV = 4,
+    ICP4R_STAGE_RECIPROCAL = 5 /* the reciprocal stage's two launches of an iteration (per-kernel timing on) */
 } icp4r_stage;
 int icp4r_stage_time_ms(icp4r_ctx* ctx, int32_t stage, double* avg_ms, int32_t* launches);
 

@@ -155,6 +155,11 @@ class IterativeClosestPoint {
     void setTransformationRotationEpsilon(double e) { params_.transformation_rotation_epsilon = e; }
     void setEuclideanFitnessEpsilon(double e) { params_.euclidean_fitness_epsilon = e; }
     double getEuclideanFitnessEpsilon() const { return params_.euclidean_fitness_epsilon; }
+    // IterativeClosestPoint::setUseReciprocalCorrespondences (PCL default false)
+    void setUseReciprocalCorrespondences(bool use_reciprocal_correspondence) {
+        params_.use_reciprocal_correspondences = use_reciprocal_correspondence ? 1 : 0;
+    }
+    bool getUseReciprocalCorrespondences() const { return params_.use_reciprocal_correspondences != 0; }
     // build extensions (no PCL counterpart)
     void setHuberDelta(double delta) { params_.huber_delta = delta; }
     void setNumerics(icp4r_numerics n) { params_.numerics = n; }
