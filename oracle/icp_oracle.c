@@ -7,7 +7,9 @@
  * SURVEY.md Appendix A, which restates upstream:
  *   PCL 1.8.1  registration/impl/icp.hpp                       computeTransformation, transformCloud
  *   PCL 1.8.1  registration/impl/registration.hpp              align, getFitnessScore
- *   PCL 1.8.1  registration/impl/correspondence_estimation.hpp determineCorrespondences
+ *   PCL 1.8.1  registration/impl/correspondence_estimation.hpp determineCorrespondences and, with
+ *              use_reciprocal_correspondences, determineReciprocalCorrespondences (the parity
+ *              matrix of the flag is tests/test_reciprocal_params.py)
  *   PCL 1.8.1  registration/impl/transformation_estimation_svd.hpp (use_umeyama_ = true)
  *   PCL 1.8.1  registration/impl/default_convergence_criteria.hpp  hasConverged
  *   Eigen 3.3  Geometry/Umeyama.h (umeyama, with_scaling = false), JacobiSVD<Matrix3f>
@@ -976,13 +978,23 @@ int oracle_align(const float* src, int32_t n, int32_t src_stride, const float* t
     int32_t cnt = 0;
     g_leaf_visits = 0;
     do {
-        /* determineCorrespondences(correspondences, corr_dist_threshold_) */
+        /* determineCorrespondences(correspondences, corr_dist_threshold_), or with
+         * use_reciprocal_correspondences determineReciprocalCorrespondences (the fitness pass below
+         * is never reciprocal) */
         cnt = 0;
         for (int32_t i = 0; i < n; ++i) {
             int32_t j;
             float d2;
             nn_query(&nn, X + 3 * (size_t)i, &j, &d2);
             if ((double)d2 > max_dist_sqr) continue;
+            if (p.use_reciprocal_correspondences) {
+                /* determineReciprocalCorrespondences: tree_reciprocal_ holds the moved source; the
+                 * exact nearest neighbour of t_j in it must be i itself, within the threshold */
+                int32_t ri;
+                float rd2;
+                brute_nearest(X, n, 3, tgt + (size_t)j * tgt_stride, &ri, &rd2);
+                if ((double)rd2 > max_dist_sqr || ri != i) continue;
+            }
             cq[cnt] = i;
             cm[cnt] = j;
             cd[cnt] = d2;

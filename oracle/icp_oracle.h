@@ -51,6 +51,12 @@ typedef struct oracle_params {
      * of its SIMD build (0: 8 = SSE without FMA). */
     int32_t eigen_l1_bytes;
     int32_t eigen_gebp_mr;
+    /* IterativeClosestPoint::setUseReciprocalCorrespondences (default false): keep (i, j) only if
+     * the exact nearest neighbour of t_j in the moved source is i, within the threshold
+     * (determineReciprocalCorrespondences).  tests/test_reciprocal.py pins it to the numpy twin;
+     * tests/test_reciprocal_params.py holds the product's parity matrix with the flag on. */
+    int32_t use_reciprocal_correspondences;
+    int32_t pad_;
 } oracle_params;
 
 /* The sigma GEMM's depth blocking (umeyama_f32): Eigen's largest panel depth for these host

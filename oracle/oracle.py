@@ -37,6 +37,8 @@ class OracleParams(C.Structure):
         ("fitness_max_range", C.c_double),
         ("eigen_l1_bytes", C.c_int32),
         ("eigen_gebp_mr", C.c_int32),
+        ("use_reciprocal_correspondences", C.c_int32),
+        ("pad_", C.c_int32),
     ]
 
 

@@ -146,6 +146,14 @@ int main(void) {
     if (oracle_align(src, N, 4, tgt, M, 4, NULL, &p, &r, NULL, NULL) != 0) return 2;
     if (oracle_align(src, N, 4, tgt, 0, 4, NULL, &p, &r, NULL, NULL) != -2) return 3;
     if (oracle_align(src, 2, 4, tgt, M, 4, NULL, &p, &r, NULL, NULL) != -3) return 4;
+    /* reciprocal correspondences: the scan of the moved source for every candidate's target (the
+     * source wraps round the target, so sources i and i + M compete and the rule rejects some) */
+    oracle_params_default(&p);
+    p.use_reciprocal_correspondences = 1;
+    p.max_iterations = 5;
+    if (oracle_align(src, N, 4, tgt, M, 4, NULL, &p, &r, out, NULL) != 0) return 7;
+    if (r.n_correspondences <= 0 || r.n_correspondences >= N) return 8;
+    if (oracle_align(src, 2, 4, tgt, M, 4, NULL, &p, &r, NULL, NULL) != -3) return 9;
     int32_t* idx = malloc(sizeof(int32_t) * N);
     float* d2 = malloc(sizeof(float) * N);
     if (oracle_nearest(src, N, 4, tgt, M, 4, 0, idx, d2) != 0) return 5;

@@ -166,6 +166,10 @@ def test_plan_options_keep_single_pair_bits(gpu_ctx, plan, seed, n, m):
 
 
 def test_plan_options_keep_batch_bits(gpu_ctx, plan):
+    """groups = 3 runs on 384 pairs (the 256 and their first 128 again): run_pairs lowers `groups` while a
+    group would hold fewer than 128 pairs, so on 256 pairs the option never formed three groups.  That
+    three groups really run is asserted from the stage's launch count in
+    test_reciprocal_params.test_stage_launch_counts[lds-3groups]."""
     import icp4r
 
     uniq = _batch_pairs()
@@ -178,9 +182,10 @@ def test_plan_options_keep_batch_bits(gpu_ctx, plan):
             kw = o
         else:
             plan(**o)
-        res = _batch(gpu_ctx, pairs, _params(max_iterations=6, **kw))
-        for i in range(len(pairs)):
-            assert_same_rows(res[i], ref[i], (o, i))
+        run = pairs + pairs[:128] if o == {"groups": 3} else pairs
+        res = _batch(gpu_ctx, run, _params(max_iterations=6, **kw))
+        for i in range(len(run)):
+            assert_same_rows(res[i], ref[i % len(pairs)], (o, i))
 
 
 # ---- 4. tie to the C oracle: a pair on which the reciprocal rule rejects nothing

@@ -31,8 +31,9 @@ def _g(x: float) -> str:
     return "%.15g" % x
 
 
-def oracle_replay(folder: str, oracle, seed: int):
-    """The node's loop (:263-721) over the oracle: returns the expected file contents.  Every frame's
+def oracle_replay(folder: str, oracle, seed: int, reciprocal: bool = False):
+    """The node's loop (:263-721) over the oracle (reciprocal: with setUseReciprocalCorrespondences(true),
+    the replay's --reciprocal): returns the expected file contents.  Every frame's
     points are appended to the running clouds, which are cleared only after a registration (:505 vs
     :698-699): an empty scan carries the other cloud's points into the next frame."""
     frames = []
@@ -59,7 +60,8 @@ def oracle_replay(folder: str, oracle, seed: int):
         acc_src = np.concatenate([acc_src, synth.records_to_xyzi(curr)])
         acc_tgt = np.concatenate([acc_tgt, synth.records_to_xyzi(last)])
         if len(acc_src) and len(acc_tgt):
-            o = oracle.align(acc_src, acc_tgt, numerics=oracle.NUM_F32)
+            o = oracle.align(acc_src, acc_tgt, numerics=oracle.NUM_F32,
+                             use_reciprocal_correspondences=1 if reciprocal else 0)
             pairs.append((k, len(acc_src), len(acc_tgt)))
             T = o["T"].astype(np.float64)
             icp_lines.append(" ".join(_g(v) for v in [T[0, 0], T[0, 1], T[0, 2], T[0, 3], T[1, 0], T[1, 1], T[1, 2],
@@ -81,8 +83,8 @@ def _run_replay(folder, seed, batch, csv, extra=()):
     return files
 
 
-def _check_against_oracle(got, folder, oracle_mod, seed, v=None):
-    pcl_info, vel, icp_lines, csv_rows, pairs = oracle_replay(str(folder), oracle_mod, seed)
+def _check_against_oracle(got, folder, oracle_mod, seed, v=None, reciprocal=False):
+    pcl_info, vel, icp_lines, csv_rows, pairs = oracle_replay(str(folder), oracle_mod, seed, reciprocal)
     assert got["pcl_info.txt"].splitlines() == pcl_info
     assert got["icp.txt"].splitlines() == icp_lines
     assert got["icp_map.txt"] == ""
