@@ -66,6 +66,11 @@ GATE_EXPORTED_SYMBOLS = [
     "icp4r_compact_by_mask_batch_device", "icp4r_static_clouds_batch_device", "icp4r_static_cloud",
     "icp4r_sequence_pairs", "icp4r_register_static_sequence", "icp4r_register_static_sequence_ex",
 ]
+# include/icp4r/icp4r_reve.h (3D Doppler ego velocity and inlier scans; icp4r.reve)
+REVE_EXPORTED_SYMBOLS = [
+    "icp4r_reve_params_default", "icp4r_reve_ransac_iterations", "icp4r_reve_draw", "icp4r_reve_batch_device",
+    "icp4r_reve_inlier_clouds_batch_device", "icp4r_reve_estimate", "icp4r_reve_inlier_cloud",
+]
 # include/icp4r/icp4r_gicp.h (generalized ICP; icp4r.gicp)
 GICP_EXPORTED_SYMBOLS = [
     "icp4r_gicp_params_default", "icp4r_gicp_align", "icp4r_gicp_align_batch_device", "icp4r_gicp_covariances",
