@@ -848,7 +848,8 @@ int icp4r_destroy(icp4r_ctx* ctx) {
                       &ctx->ego_pd, &ctx->ego_scores, &ctx->ego_res, &ctx->ego_mask, &ctx->ego_xyzi, &ctx->gicp_gs,
                       &ctx->gicp_cov_src, &ctx->gicp_cov_tgt, &ctx->gicp_mah, &ctx->gicp_active, &ctx->gicp_part, &ctx->gicp_sidx, &ctx->vox_work,
                       &ctx->vox_in, &ctx->vox_out, &ctx->vox_cnt, &ctx->gate_counts, &ctx->gate_base, &ctx->gate_cnt,
-                      &ctx->gate_bad, &ctx->gate_mask, &ctx->gate_clouds, &ctx->gate_pair_off, &ctx->gate_pair_n})
+                      &ctx->gate_bad, &ctx->gate_mask, &ctx->gate_clouds, &ctx->gate_pair_off, &ctx->gate_pair_n,
+                      &ctx->vgicp_work, &ctx->vgicp_cov})
         b->release();
     for (auto* v : {&ctx->nn_events, &ctx->test_events, &ctx->upd_events, &ctx->batch_events, &ctx->recip_events,
                     &ctx->gicp_events, &ctx->vox_events})

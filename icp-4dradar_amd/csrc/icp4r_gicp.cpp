@@ -25,6 +25,7 @@
 
 #include "icp4r/icp4r_gicp.h"
 #include "icp4r_batch.hpp"
+#include "icp4r_gicp_host.hpp"
 #include "icp4r_host.hpp"
 #include "icp4r_internal.hpp"
 
@@ -65,7 +66,9 @@ int wait_active(volatile int64_t* slot, uint32_t seq, hipStream_t st, int32_t* o
     }
 }
 
-int check_params(const icp4r_gicp_params* p) {
+}  // namespace
+
+int icp4r_gicp_host::check_params(const icp4r_gicp_params* p) {
     if (p->k_correspondences < 1 || p->k_correspondences > 32)
         return fail(ICP4R_E_INVALID, "k_correspondences %d outside [1, 32]", p->k_correspondences);
     if (p->max_iterations < 0) return fail(ICP4R_E_INVALID, "max_iterations < 0");
@@ -77,6 +80,8 @@ int check_params(const icp4r_gicp_params* p) {
     if (!(p->max_correspondence_distance > 0)) return fail(ICP4R_E_INVALID, "max_correspondence_distance must be > 0");
     return ICP4R_OK;
 }
+
+namespace {
 
 // Brute force or pruned k-NN for the covariances: brute force where the plan does not prune, or with
 // plan option gicp_cov_brute = 1 (A/B and the equality test). (Brute force by default for small
@@ -124,19 +129,22 @@ int cov_pass(const icp4r_pipe::Plan& pl, const PairArgs& a, const WorkArgs& w, c
     return ICP4R_OK;
 }
 
-// The registration of a device-resident batch (pointers in `a`), results into a.results.
-int run_gicp(icp4r_ctx* ctx, const PairArgs& a, int npairs, int max_n, int max_m, const icp4r_gicp_params& gp,
-             hipStream_t st) {
+}  // namespace
+
+int icp4r_gicp_host::begin(icp4r_ctx* ctx, const PairArgs& a, int npairs, int max_n, int max_m,
+                           const icp4r_gicp_params& gp, bool nn_index, hipStream_t st, Work& k) {
     using namespace icp4r_pipe;
-    if (npairs <= 0) return ICP4R_OK;
-    const int mn = max_n > 0 ? max_n : 1;
-    const int mm = max_m > 0 ? max_m : 1;
+    const int mn = k.mn = max_n > 0 ? max_n : 1;
+    const int mm = k.mm = max_m > 0 ? max_m : 1;
+    Plan& pl = k.pl;
+    WorkArgs& w = k.w;
+    GicpArgs& g = k.g;
+    EventPair*& be = k.be;
     // pruned plans index the source too (its k-NN covariances): the index strides fit both clouds,
     // and the batched search, which stages t_stride targets, only runs when those fit its LDS
     const int idx_both = max_n > max_m ? max_n : max_m;
-    Plan pl = make_plan(ctx, npairs, mn, max_m, ICP4R_NN_AUTO, idx_both <= kLdsMaxTargets);
+    pl = make_plan(ctx, npairs, mn, max_m, ICP4R_NN_AUTO, idx_both <= kLdsMaxTargets);
     pl.cache = false;  // the iteration kernels move X without maintaining the cached-neighbour bounds
-    WorkArgs w;
     int rc;
     const int idx_m = pl.pruned ? idx_both : max_m;
     if ((rc = setup_work(ctx, pl, npairs, max_n, idx_m, false, st, w))) return rc;
@@ -152,7 +160,6 @@ int run_gicp(icp4r_ctx* ctx, const PairArgs& a, int npairs, int max_n, int max_m
     const size_t err_b = (size_t)npairs * kGicpMaxSlices * kGicpSpec * sizeof(double);
     const size_t cand_b = (size_t)npairs * sizeof(GicpCand);
     HIP_TRY(ctx->gicp_part.ensure(lin_b + err_b + cand_b + (size_t)npairs * sizeof(int32_t)));
-    GicpArgs g;
     g.gs = static_cast<GicpState*>(ctx->gicp_gs.p);
     g.cov_src = static_cast<const double*>(ctx->gicp_cov_src.p);
     g.cov_tgt = static_cast<const double*>(ctx->gicp_cov_tgt.p);
@@ -177,7 +184,6 @@ int run_gicp(icp4r_ctx* ctx, const PairArgs& a, int npairs, int max_n, int max_m
     const int grid = opt(ctx, kOptGicpGrid, kGicpGrid);
     g.grid = grid < 1 ? 1 : grid;
 
-    EventPair* be;
     if ((rc = next_event(ctx->batch_events, ctx->batch_used, &be))) return rc;
     HIP_TRY(hipEventRecord(be->start, st));
     HIP_TRY(launch_init(a, w, npairs, st));
@@ -248,26 +254,30 @@ int run_gicp(icp4r_ctx* ctx, const PairArgs& a, int npairs, int max_n, int max_m
                            gp.regularization, ct, st, brute, true, knn_lanes)))
             return rc;
     }
-    if (pl.pruned && brute) HIP_TRY(launch_index(a, w, npairs, st));
+    k.indexed = !pl.pruned || !brute;
+    if (!k.indexed && nn_index) {
+        HIP_TRY(launch_index(a, w, npairs, st));
+        k.indexed = true;
+    }
     if (kev) HIP_TRY(hipEventRecord(ce->stop, st));
     ctx->gicp_last_pairs = npairs;
     ctx->gicp_last_xs = xs;
     ctx->gicp_last_ts = ts;
+    return ICP4R_OK;
+}
+
+int icp4r_gicp_host::iterate(icp4r_ctx* ctx, const Work& k, int npairs, int max_iterations, hipStream_t st,
+                             const std::function<int(int)>& step) {
+    const WorkArgs& w = k.w;
+    int rc;
     int32_t* active = static_cast<int32_t*>(ctx->gicp_active.p);
     if (!ctx->gicp_hflag) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&ctx->gicp_hflag), 2 * sizeof(int64_t), hipHostMallocCoherent));
     volatile int64_t* hf = ctx->gicp_hflag;
     int nchk = 0, prev_slot = -1;
     uint32_t prev_seq = 0;
-    for (int it = 0; it < gp.max_iterations; ++it) {
-        if ((rc = nn_pass(ctx, pl, a, w, npairs, mn, 0, it == 0, st))) return rc;
-        EventPair* ue = nullptr;
-        if (kev) {
-            if ((rc = next_event(ctx->upd_events, ctx->upd_used, &ue))) return rc;
-            HIP_TRY(hipEventRecord(ue->start, st));
-        }
-        HIP_TRY(launch_gicp_iter(a, w, g, npairs, mn, it, st));
-        if (kev) HIP_TRY(hipEventRecord(ue->stop, st));
-        if ((it + 1) % kActiveCheck == 0 && it + 1 < gp.max_iterations) {
+    for (int it = 0; it < max_iterations; ++it) {
+        if ((rc = step(it))) return rc;
+        if ((it + 1) % kActiveCheck == 0 && it + 1 < max_iterations) {
             const int slot = nchk++ & 1;  // (the previous check's slot is the other one; the one before
             hf[slot] = -1;                // was read before that check was queued)
             const uint32_t seq = ++ctx->gicp_seq;
@@ -281,14 +291,54 @@ int run_gicp(icp4r_ctx* ctx, const PairArgs& a, int npairs, int max_n, int max_m
             prev_seq = seq;
         }
     }
-    if (a.kp.compute_fitness || a.aligned) HIP_TRY(launch_fitness_prep(a, w, npairs, st));
-    if (a.kp.compute_fitness && (rc = nn_pass(ctx, pl, a, w, npairs, mn, 1, 0, st))) return rc;
-    HIP_TRY(launch_finish(a, w, npairs, st));
-    HIP_TRY(hipEventRecord(be->stop, st));
     return ICP4R_OK;
 }
 
-int gicp_kparams(const icp4r_gicp_params& gp, KParams* kp) {
+int icp4r_gicp_host::end(icp4r_ctx* ctx, const PairArgs& a, Work& k, int npairs, bool first_nn, hipStream_t st) {
+    const WorkArgs& w = k.w;
+    int rc;
+    if (a.kp.compute_fitness || a.aligned) HIP_TRY(launch_fitness_prep(a, w, npairs, st));
+    if (a.kp.compute_fitness) {
+        if (!k.indexed) {
+            HIP_TRY(launch_index(a, w, npairs, st));
+            k.indexed = true;
+        }
+        if ((rc = icp4r_pipe::nn_pass(ctx, k.pl, a, w, npairs, k.mn, 1, first_nn ? 1 : 0, st))) return rc;
+    }
+    HIP_TRY(launch_finish(a, w, npairs, st));
+    HIP_TRY(hipEventRecord(k.be->stop, st));
+    return ICP4R_OK;
+}
+
+namespace {
+
+// The registration of a device-resident batch (pointers in `a`), results into a.results.
+int run_gicp(icp4r_ctx* ctx, const PairArgs& a, int npairs, int max_n, int max_m, const icp4r_gicp_params& gp,
+             hipStream_t st) {
+    if (npairs <= 0) return ICP4R_OK;
+    icp4r_gicp_host::Work k;
+    int rc;
+    if ((rc = icp4r_gicp_host::begin(ctx, a, npairs, max_n, max_m, gp, true, st, k))) return rc;
+    const bool kev = ctx->kernel_timing;
+    auto step = [&](int it) -> int {
+        int rc;
+        if ((rc = icp4r_pipe::nn_pass(ctx, k.pl, a, k.w, npairs, k.mn, 0, it == 0, st))) return rc;
+        EventPair* ue = nullptr;
+        if (kev) {
+            if ((rc = icp4r_pipe::next_event(ctx->upd_events, ctx->upd_used, &ue))) return rc;
+            HIP_TRY(hipEventRecord(ue->start, st));
+        }
+        HIP_TRY(launch_gicp_iter(a, k.w, k.g, npairs, k.mn, it, st));
+        if (kev) HIP_TRY(hipEventRecord(ue->stop, st));
+        return ICP4R_OK;
+    };
+    if ((rc = icp4r_gicp_host::iterate(ctx, k, npairs, gp.max_iterations, st, step))) return rc;
+    return icp4r_gicp_host::end(ctx, a, k, npairs, false, st);
+}
+
+}  // namespace
+
+int icp4r_gicp_host::kparams(const icp4r_gicp_params& gp, KParams* kp) {
     icp4r_params ip;
     icp4r_params_default(&ip);
     ip.compute_fitness = gp.compute_fitness;
@@ -298,40 +348,12 @@ int gicp_kparams(const icp4r_gicp_params& gp, KParams* kp) {
     return ICP4R_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-void icp4r_gicp_params_default(icp4r_gicp_params* p) {
-    if (!p) return;
-    memset(p, 0, sizeof(*p));
-    p->k_correspondences = 20;
-    p->max_iterations = 64;
-    p->rotation_epsilon = 2e-3;
-    p->transformation_epsilon = 5e-4;
-    p->max_correspondence_distance = FLT_MAX;
-    p->regularization = ICP4R_GICP_REG_PLANE;
-    p->lm_max_iterations = 10;
-    p->lm_init_lambda_factor = 1e-9;
-    p->compute_fitness = 1;
-}
-
-int icp4r_gicp_align_batch_device(icp4r_ctx* ctx, const icp4r_batch* b, const icp4r_gicp_params* params,
-                                  icp4r_result* results, void* hip_stream) {
-    if (!ctx || !b || !results) return fail(ICP4R_E_INVALID, "ctx/batch/results is NULL");
+int icp4r_gicp_host::pair_args(const icp4r_batch* b, icp4r_result* results, PairArgs& a) {
     if (b->npairs < 0) return fail(ICP4R_E_INVALID, "npairs < 0");
     if (b->npairs == 0) return ICP4R_OK;
     if (!b->src || !b->tgt || !b->src_off || !b->src_n || !b->tgt_off || !b->tgt_n)
         return fail(ICP4R_E_INVALID, "batch has a NULL device array");
     if (b->max_src_n < 0 || b->max_tgt_n < 0) return fail(ICP4R_E_INVALID, "negative max sizes");
-    icp4r_gicp_params gp;
-    if (params) gp = *params;
-    else icp4r_gicp_params_default(&gp);
-    int rc;
-    if ((rc = check_params(&gp))) return rc;
-    PairArgs a;
-    if ((rc = gicp_kparams(gp, &a.kp))) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
     a.src = reinterpret_cast<const float4*>(b->src);
     a.tgt = reinterpret_cast<const float4*>(b->tgt);
     a.src_off = b->src_off;
@@ -341,13 +363,13 @@ int icp4r_gicp_align_batch_device(icp4r_ctx* ctx, const icp4r_batch* b, const ic
     a.guess = b->guess;
     a.aligned = reinterpret_cast<float4*>(b->aligned);
     a.results = reinterpret_cast<Result*>(results);
-    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->stream;
-    return run_gicp(ctx, a, b->npairs, b->max_src_n, b->max_tgt_n, gp, st);
+    return ICP4R_OK;
 }
 
-int icp4r_gicp_align(icp4r_ctx* ctx, const float* src, int32_t n, int32_t src_stride_bytes, const float* tgt,
-                     int32_t m, int32_t tgt_stride_bytes, const float* guess, const icp4r_gicp_params* params,
-                     icp4r_result* out, float* aligned_out, int32_t out_stride_bytes) {
+int icp4r_gicp_host::align_host(icp4r_ctx* ctx, const float* src, int32_t n, int32_t src_stride_bytes, const float* tgt,
+                                int32_t m, int32_t tgt_stride_bytes, const float* guess, icp4r_result* out,
+                                float* aligned_out, int32_t out_stride_bytes, const char* who,
+                                const std::function<int(const icp4r_batch&, icp4r_result*, hipStream_t)>& run) {
     using namespace icp4r_host;
     if (!ctx || !out) return fail(ICP4R_E_INVALID, "ctx/out is NULL");
     int rc;
@@ -390,7 +412,7 @@ int icp4r_gicp_align(icp4r_ctx* ctx, const float* src, int32_t n, int32_t src_st
     b.npairs = 1;
     b.max_src_n = n;
     b.max_tgt_n = m;
-    if ((rc = icp4r_gicp_align_batch_device(ctx, &b, params, static_cast<icp4r_result*>(ctx->results.p), st))) return rc;
+    if ((rc = run(b, static_cast<icp4r_result*>(ctx->results.p), st))) return rc;
     HIP_TRY(hipMemcpyAsync(out, ctx->results.p, sizeof(icp4r_result), hipMemcpyDeviceToHost, st));
     std::vector<float> ha;
     if (aligned_out && n > 0) {
@@ -412,9 +434,51 @@ int icp4r_gicp_align(icp4r_ctx* ctx, const float* src, int32_t n, int32_t src_st
         const char* what = out->status == ICP4R_E_EMPTY ? "No input target dataset was given!"
                            : out->status == ICP4R_E_NONFINITE ? "non-finite coordinate in an input cloud"
                                                               : "registration failed";
-        return fail(out->status, "[icp4r::FastGICP::computeTransformation] %s", what);
+        return fail(out->status, "[icp4r::%s::computeTransformation] %s", who, what);
     }
     return ICP4R_OK;
+}
+
+extern "C" {
+
+void icp4r_gicp_params_default(icp4r_gicp_params* p) {
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->k_correspondences = 20;
+    p->max_iterations = 64;
+    p->rotation_epsilon = 2e-3;
+    p->transformation_epsilon = 5e-4;
+    p->max_correspondence_distance = FLT_MAX;
+    p->regularization = ICP4R_GICP_REG_PLANE;
+    p->lm_max_iterations = 10;
+    p->lm_init_lambda_factor = 1e-9;
+    p->compute_fitness = 1;
+}
+
+int icp4r_gicp_align_batch_device(icp4r_ctx* ctx, const icp4r_batch* b, const icp4r_gicp_params* params,
+                                  icp4r_result* results, void* hip_stream) {
+    if (!ctx || !b || !results) return fail(ICP4R_E_INVALID, "ctx/batch/results is NULL");
+    int rc;
+    PairArgs a;
+    if ((rc = icp4r_gicp_host::pair_args(b, results, a)) || b->npairs == 0) return rc;
+    icp4r_gicp_params gp;
+    if (params) gp = *params;
+    else icp4r_gicp_params_default(&gp);
+    if ((rc = icp4r_gicp_host::check_params(&gp))) return rc;
+    if ((rc = icp4r_gicp_host::kparams(gp, &a.kp))) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->stream;
+    return run_gicp(ctx, a, b->npairs, b->max_src_n, b->max_tgt_n, gp, st);
+}
+
+int icp4r_gicp_align(icp4r_ctx* ctx, const float* src, int32_t n, int32_t src_stride_bytes, const float* tgt,
+                     int32_t m, int32_t tgt_stride_bytes, const float* guess, const icp4r_gicp_params* params,
+                     icp4r_result* out, float* aligned_out, int32_t out_stride_bytes) {
+    return icp4r_gicp_host::align_host(ctx, src, n, src_stride_bytes, tgt, m, tgt_stride_bytes, guess, out, aligned_out,
+                                       out_stride_bytes, "FastGICP",
+                                       [&](const icp4r_batch& b, icp4r_result* res, hipStream_t st) {
+                                           return icp4r_gicp_align_batch_device(ctx, &b, params, res, st);
+                                       });
 }
 
 int icp4r_gicp_covariances(icp4r_ctx* ctx, const float* cloud, int32_t n, int32_t stride_bytes, int32_t k,

@@ -26,6 +26,7 @@
 #include <stdint.h>
 
 #include "icp4r_device.hpp"
+#include "icp4r_gicp_dev.hpp"
 #include "icp4r_internal.hpp"
 #include "icp4r_math.hpp"
 
@@ -81,22 +82,6 @@ __device__ void gicp_sym_eig3(const double* a_in, double* w, double* V) {
             }
 }
 
-// Eigen-style cofactor inverse of a 3x3 (row-major)
-__device__ __forceinline__ void gicp_inv3(const double* m, double* r) {
-    const double c0 = m[4] * m[8] - m[5] * m[7];
-    const double c1 = m[7] * m[2] - m[8] * m[1];
-    const double c2 = m[1] * m[5] - m[2] * m[4];
-    const double id = 1.0 / (c0 * m[0] + c1 * m[3] + c2 * m[6]);
-    r[0] = c0 * id;
-    r[1] = c1 * id;
-    r[2] = c2 * id;
-    r[3] = (m[5] * m[6] - m[3] * m[8]) * id;
-    r[4] = (m[8] * m[0] - m[6] * m[2]) * id;
-    r[5] = (m[2] * m[3] - m[0] * m[5]) * id;
-    r[6] = (m[3] * m[7] - m[4] * m[6]) * id;
-    r[7] = (m[6] * m[1] - m[7] * m[0]) * id;
-    r[8] = (m[0] * m[4] - m[1] * m[3]) * id;
-}
 
 // fast_gicp::RegularizationMethod applied to a 3x3 covariance (row-major, symmetric)
 __device__ void gicp_regularize(const double* c, int reg, double* o) {
@@ -383,214 +368,8 @@ __global__ __launch_bounds__(kCovWG) void gicp_knn_cov_kernel(const float4* __re
     gicp_cov_from_knn<K>(best, min(k, n), reg, cloud + off[p], n, cov_out + ((int64_t)p * stride + oi) * 6);
 }
 
-// ---- per-iteration update
-constexpr int kGicpSliceWG = 256;  // threads per slice workgroup; a slice is a multiple of it
-constexpr int kGicpSliceWaves = kGicpSliceWG / 64;
-// (the linearisation's deciding workgroup hands out its copies by thread ranges up to thread 140)
-static_assert(kGicpSliceWG >= 128 + 12 && kGicpSliceWG >= kGicpSpec * 12, "slice workgroup too small");
-
-// points per slice and slices of an n-point source: at least one slice (an empty source still
-// decides), at most kGicpMaxSlices, a slice a multiple of kGicpSliceWG points
-__host__ __device__ __forceinline__ int gicp_slice_pts(int n) {
-    const int m = (n + kGicpSliceWG * kGicpMaxSlices - 1) / (kGicpSliceWG * kGicpMaxSlices);
-    return kGicpSliceWG * (m > 1 ? m : 1);
-}
-__host__ __device__ __forceinline__ int gicp_slices(int n) {
-    const int s = (n + gicp_slice_pts(n) - 1) / gicp_slice_pts(n);
-    return s > 1 ? s : 1;
-}
-
-__device__ __forceinline__ void sym_unpack(const double* s, double* m) {
-    m[0] = s[0]; m[1] = s[1]; m[2] = s[2];
-    m[3] = s[1]; m[4] = s[3]; m[5] = s[4];
-    m[6] = s[2]; m[7] = s[4]; m[8] = s[5];
-}
-
-// so3_exp (fast_gicp so3.hpp) then Eigen's Quaternion::toRotationMatrix
-__device__ void gicp_so3_exp(const double* w, double* R) {
-    const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
-    double imag, real;
-    if (th2 < 1e-10) {
-        const double th4 = th2 * th2;
-        imag = 0.5 - 1.0 / 48.0 * th2 + 1.0 / 3840.0 * th4;
-        real = 1.0 - 1.0 / 8.0 * th2 + 1.0 / 384.0 * th4;
-    } else {
-        const double th = sqrt(th2), half = 0.5 * th;
-        imag = sin(half) / th;
-        real = cos(half);
-    }
-    const double qw = real, qx = imag * w[0], qy = imag * w[1], qz = imag * w[2];
-    const double tx = 2 * qx, ty = 2 * qy, tz = 2 * qz;
-    const double twx = tx * qw, twy = ty * qw, twz = tz * qw, txx = tx * qx, txy = ty * qx, txz = tz * qx;
-    const double tyy = ty * qy, tyz = tz * qy, tzz = tz * qz;
-    R[0] = 1 - (tyy + tzz); R[1] = txy - twz; R[2] = txz + twy;
-    R[3] = txy + twz; R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
-    R[6] = txz - twy; R[7] = tyz + twx; R[8] = 1 - (txx + tyy);
-}
-
-// (A) x = b, A symmetric positive definite 6x6 (row-major), LDLᵀ without pivoting; L overwrites A's
-// strict lower triangle (each A[i][j], i > j, is read once, just before L[i][j] replaces it: the same
-// operations in the same order as with a separate L, in a third of the registers — the separate 6x6
-// arrays beside the LM state had spilled the iteration kernel to scratch)
-__device__ void gicp_ldlt6(double (&A)[36], const double (&b)[6], double (&x)[6]) {
-    double D[6], y[6];
-    for (int j = 0; j < 6; ++j) {
-        double s = A[6 * j + j];
-        for (int k = 0; k < j; ++k) s -= A[6 * j + k] * A[6 * j + k] * D[k];
-        D[j] = s;
-        for (int i = j + 1; i < 6; ++i) {
-            double t = A[6 * i + j];
-            for (int k = 0; k < j; ++k) t -= A[6 * i + k] * A[6 * j + k] * D[k];
-            A[6 * i + j] = D[j] != 0.0 ? t / D[j] : t;  // Eigen: a zero pivot leaves its column undivided
-        }
-    }
-    for (int i = 0; i < 6; ++i) {
-        double s = b[i];
-        for (int k = 0; k < i; ++k) s -= A[6 * i + k] * y[k];
-        y[i] = s;
-    }
-    for (int i = 0; i < 6; ++i) y[i] = fabs(D[i]) > DBL_MIN ? y[i] / D[i] : 0.0;  // Eigen's LDLT::solve
-    for (int i = 5; i >= 0; --i) {
-        double s = y[i];
-        for (int k = i + 1; k < 6; ++k) s -= A[6 * k + i] * x[k];
-        x[i] = s;
-    }
-}
-
-__device__ __forceinline__ bool gicp_converged(const double* R, const double* t, double rot_eps, double trans_eps) {
-    double m = 0.0;
-    for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 3; ++c) m = fmax(m, 1.0 / rot_eps * fabs(R[3 * r + c] - (r == c ? 1.0 : 0.0)));
-    for (int r = 0; r < 3; ++r) m = fmax(m, 1.0 / trans_eps * fabs(t[r]));
-    return m < 1.0;
-}
-
-// the error eᵀMe of correspondence (a, b) at transform (R, t), and with LIN its terms of H = Σ JᵀMJ and
-// g = Σ JᵀMe (J = [skew(Ta), -I]) and the count, into acc (fast_gicp's linearize / compute_error)
-template <bool LIN>
-__device__ __forceinline__ void gicp_point(const float4 sa, const float4 sb, const double (&M)[9], const double* R,
-                                           const double* t, double* acc) {
-    const double a[3] = {sa.x, sa.y, sa.z};
-    double ta[3];
-    for (int r = 0; r < 3; ++r) ta[r] = R[3 * r] * a[0] + R[3 * r + 1] * a[1] + R[3 * r + 2] * a[2] + t[r];
-    const double e[3] = {(double)sb.x - ta[0], (double)sb.y - ta[1], (double)sb.z - ta[2]};
-    double Me[3];
-    for (int r = 0; r < 3; ++r) Me[r] = M[3 * r] * e[0] + M[3 * r + 1] * e[1] + M[3 * r + 2] * e[2];
-    if (!LIN) {
-        acc[0] += e[0] * Me[0] + e[1] * Me[1] + e[2] * Me[2];
-        return;
-    }
-    acc[27] += e[0] * Me[0] + e[1] * Me[1] + e[2] * Me[2];
-    acc[28] += 1.0;
-    // J = [skew(Ta), -I] (row k: J[k][0..2] = skew, J[k][3 + k] = -1). The terms with a zero or -1
-    // factor of J are left out or reduced to a negation: the same values as the generic JᵀMJ / JᵀMe
-    // sums (x + (+-0) = x), in half the operations.
-    auto js = [&](int k, int c) -> double {  // skew(Ta)[k][c], k != c
-        return k == 0 ? (c == 1 ? -ta[2] : ta[1]) : k == 1 ? (c == 0 ? ta[2] : -ta[0]) : (c == 0 ? -ta[1] : ta[0]);
-    };
-    double MS[9];  // M skew(Ta)
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const int k0 = c == 0 ? 1 : 0, k1 = c == 2 ? 1 : 2;
-            MS[3 * r + c] = M[3 * r + k0] * js(k0, c) + M[3 * r + k1] * js(k1, c);
-        }
-    int u = 0;
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        const int k0 = r == 0 ? 1 : 0, k1 = r == 2 ? 1 : 2;  // the rows k != r of column r of J
-#pragma unroll
-        for (int c = r; c < 3; ++c) acc[u++] += js(k0, r) * MS[3 * k0 + c] + js(k1, r) * MS[3 * k1 + c];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) acc[u++] += js(k0, r) * -M[3 * k0 + c] + js(k1, r) * -M[3 * k1 + c];
-        acc[21 + r] += js(k0, r) * Me[k0] + js(k1, r) * Me[k1];
-    }
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-#pragma unroll
-        for (int c = r; c < 3; ++c) acc[u++] += M[3 * r + c];
-        acc[24 + r] += -Me[r];
-    }
-}
-
-// Σ over the workgroup of each v[k] in a fixed order (butterfly per wave, then the waves in order);
-// the sum of v[k] is returned to thread k < NV. red: kGicpSliceWaves * NV doubles of LDS.
-template <int NV>
-__device__ __forceinline__ double gicp_slice_sum(double (&v)[NV], double* red) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_xor(v[k], off, 64);
-    }
-    if (lane == 0)
-        for (int k = 0; k < NV; ++k) red[wave * NV + k] = v[k];
-    __syncthreads();
-    double r = 0.0;
-    if (threadIdx.x < NV)
-        for (int q = 0; q < kGicpSliceWaves; ++q) r += red[q * NV + threadIdx.x];
-    __syncthreads();  // red is free again
-    return r;
-}
-
-// The same for the 29 sums of the linearisation, as a transposing reduction: at each step a lane keeps
-// half of its values and adds its partner's copy of that half (one shuffle per kept value), so the 32
-// padded values take 16 + 8 + 4 + 2 + 1 + 1 shuffles instead of 29 x 6; lanes 2k and 2k + 1 end with
-// the wave's sum of value k (another fixed order than the butterfly's). In place in v.
-__device__ __forceinline__ double gicp_slice_sum_sys(double (&v)[kGicpSys], double* red) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    {
-        const bool hi = lane & 32;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            const double lo_v = v[k], hi_v = k + 16 < kGicpSys ? v[k + 16] : 0.0;
-            v[k] = (hi ? hi_v : lo_v) + __shfl_xor(hi ? lo_v : hi_v, 32, 64);
-        }
-    }
-#pragma unroll
-    for (int h = 8, o = 16; h >= 1; h >>= 1, o >>= 1) {
-        const bool hi = lane & o;
-#pragma unroll
-        for (int k = 0; k < h; ++k) {
-            const double a = v[k], b = v[k + h];
-            v[k] = (hi ? b : a) + __shfl_xor(hi ? a : b, o, 64);
-        }
-    }
-    const double r1 = v[0] + __shfl_xor(v[0], 1, 64);
-    const int k = lane >> 1;  // the value this lane pair holds
-    if (!(lane & 1) && k < kGicpSys) red[wave * kGicpSys + k] = r1;
-    __syncthreads();
-    double r = 0.0;
-    if (threadIdx.x < kGicpSys)
-        for (int q = 0; q < kGicpSliceWaves; ++q) r += red[q * kGicpSys + threadIdx.x];
-    __syncthreads();
-    return r;
-}
-
-// the LM trial of damping lambda from the system sys at x0 = (R0, t0): delta from (H + λI) d = -g,
-// the trial transform delta * x0 (fast_gicp LsqRegistration::step_lm)
-__device__ void gicp_make_trial(const double* sys, double lambda, const double* R0, const double* t0, GicpTrial& o) {
-    double A[36], nb[6];
-    int u = 0;
-    for (int r = 0; r < 6; ++r)
-        for (int c = r; c < 6; ++c) A[6 * r + c] = A[6 * c + r] = sys[u++];
-    for (int k = 0; k < 6; ++k) A[7 * k] += lambda;
-    for (int k = 0; k < 6; ++k) nb[k] = -sys[21 + k];
-    double d[6];
-    gicp_ldlt6(A, nb, d);
-    for (int k = 0; k < 6; ++k) o.d[k] = d[k];
-    gicp_so3_exp(d, o.dR);
-    o.dt[0] = d[3];
-    o.dt[1] = d[4];
-    o.dt[2] = d[5];
-    for (int r = 0; r < 3; ++r) {
-        for (int c = 0; c < 3; ++c) o.R[3 * r + c] = o.dR[3 * r] * R0[c] + o.dR[3 * r + 1] * R0[3 + c] + o.dR[3 * r + 2] * R0[6 + c];
-        o.t[r] = o.dR[3 * r] * t0[0] + o.dR[3 * r + 1] * t0[1] + o.dR[3 * r + 2] * t0[2] + o.dt[r];
-    }
-    o.lambda = lambda;
-}
-
+// ---- per-iteration update (the slicing, one correspondence's terms, the slice reductions, the LM trial
+// and the hand-off between a pair's workgroups: icp4r_gicp_dev.hpp)
 struct GicpPairView {
     int n, ps, ns;  // points, points per slice, slices
     const float4 *src, *tgt;
@@ -608,44 +387,6 @@ __device__ __forceinline__ GicpPairView gicp_view(const PairArgs& a, const WorkA
     v.key = w.nn_key + (int64_t)p * w.x_stride;
     v.mah = g.mah + (int64_t)p * w.x_stride * 6;
     return v;
-}
-
-// Workgroup j of a pair takes its slices j, j + W, j + 2W, ... (W workgroups per pair, fewer for many pairs:
-// the slicing, and so every sum, depends on n only; W only spreads the slices over the chip).
-// The per-slice sums of one pair reach the workgroup that finishes last (the counter form of the
-// hand-off in cdna_hip_programming.md §6 Guideline 16, with write-through sum stores, gicp_publish,
-// in place of a release fence in every workgroup): every workgroup waits for its stores and draws a
-// ticket; the one drawing nw - 1 acquires, resets the counter for the next launch and returns true
-// (in all its threads).
-// This block's pair and its index j < W among the pair's workgroups: the W workgroups of a pair on one
-// XCD, as blocks are dealt round-robin over the 8 XCDs (blocks b and b + 8 share one), so a pair's
-// gathered target data is fetched into one L2, not eight (a speed choice only: nothing depends on it)
-__device__ __forceinline__ bool gicp_block(int npairs, int W, int& p, int& j) {
-    const int b = blockIdx.x, x = b & 7, r = b >> 3;
-    p = (r / W) * 8 + x;
-    j = r % W;
-    return p < npairs;
-}
-
-__device__ __forceinline__ void gicp_publish(double* p, double v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ bool gicp_last_slice(int32_t* cnt, int nw, int32_t* flag) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const int prev = __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int last = prev == nw - 1;
-        if (last) {
-            __hip_atomic_store(cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        *flag = last;
-    }
-    __syncthreads();
-    return *flag != 0;
 }
 
 // (1) update_correspondences + linearize over one slice: M_i = (C_B + R C_A Rᵀ)⁻¹ of every valid
@@ -695,6 +436,8 @@ __global__ __launch_bounds__(kGicpSliceWG) void gicp_lin_kernel(PairArgs a, Work
         if (threadIdx.x < kGicpSys) gicp_publish(part + q * kGicpSys + threadIdx.x, r);
     }
     if (!gicp_last_slice(g.cnt + p, nw, &last)) return;
+    // !! TWO COPIES: from here to the end this is gicp_lin_finish of icp4r_gicp_dev.hpp (which the voxelized
+    // kernel calls) written out in place — any fix goes into both (see that header's note).
     // the slices' sums staged in LDS by all threads at once (one round trip, not one per slice), then
     // added in slice order
     __shared__ double stage[kGicpMaxSlices * kGicpSys];
@@ -790,6 +533,8 @@ __global__ __launch_bounds__(kGicpSliceWG) void gicp_trial_kernel(PairArgs a, Wo
             if (threadIdx.x < kGicpSpec) gicp_publish(part + q * kGicpSpec + threadIdx.x, r);
         }
         if (!gicp_last_slice(g.cnt + p, nw, &last)) return;
+        // !! TWO COPIES: from here to the end this is gicp_trial_finish of icp4r_gicp_dev.hpp (which the
+        // voxelized kernel calls) written out in place — any fix goes into both (see that header's note).
         __shared__ double stage[kGicpMaxSlices * kGicpSpec];  // (as in the linearisation)
         for (int e = threadIdx.x; e < ns * kGicpSpec; e += kGicpSliceWG) stage[e] = part[e];
         __syncthreads();
@@ -1007,11 +752,10 @@ hipError_t launch_gicp_knn_cov(const float4* cloud, const int64_t* off, const in
 hipError_t launch_gicp_iter(const PairArgs& a, const WorkArgs& w, const GicpArgs& g, int npairs, int max_n, int it,
                             hipStream_t st) {
     if (npairs <= 0) return hipSuccess;
-    // about g.grid workgroups in all (a single pair: one per slice)
-    const int ns = gicp_slices(max_n);
-    const int per = g.grid / npairs;
-    const int W = per < 1 ? 1 : per > ns ? ns : per;
-    const dim3 grid((unsigned)W * ((npairs + 7) / 8 * 8)), block(kGicpSliceWG);
+    int W;
+    unsigned blocks;
+    gicp_iter_grid(npairs, max_n, g.grid, W, blocks);
+    const dim3 grid(blocks), block(kGicpSliceWG);
     hipLaunchKernelGGL(gicp_lin_kernel, grid, block, 0, st, a, w, g, npairs, W);
     hipLaunchKernelGGL(gicp_trial_kernel, grid, block, 0, st, a, w, g, npairs, W, it);
     hipLaunchKernelGGL(gicp_move_kernel, grid, block, 0, st, a, w, g, npairs, W);

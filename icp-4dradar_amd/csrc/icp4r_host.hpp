@@ -154,4 +154,7 @@ struct icp4r_ctx {
     // the Doppler gate (icp4r_gate.cpp): the compaction's workspace (tile counts and bases), the guarded
     // counts and flags, the mask when the caller keeps none, the host entries' packed clouds and descriptors
     icp4r_host::DevBuf gate_counts, gate_base, gate_cnt, gate_bad, gate_mask, gate_clouds, gate_pair_off, gate_pair_n;
+    // voxelized GICP (icp4r_vgicp.cpp): the voxel maps and stored correspondences (icp4r::VgicpLayout); the
+    // covariances icp4r_vgicp_voxel_map was given
+    icp4r_host::DevBuf vgicp_work, vgicp_cov;
 };

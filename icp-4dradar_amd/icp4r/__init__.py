@@ -75,6 +75,10 @@ REVE_EXPORTED_SYMBOLS = [
 GICP_EXPORTED_SYMBOLS = [
     "icp4r_gicp_params_default", "icp4r_gicp_align", "icp4r_gicp_align_batch_device", "icp4r_gicp_covariances",
 ]
+# include/icp4r/icp4r_vgicp.h (voxelized generalized ICP; icp4r.vgicp)
+VGICP_EXPORTED_SYMBOLS = [
+    "icp4r_vgicp_params_default", "icp4r_vgicp_align", "icp4r_vgicp_align_batch_device", "icp4r_vgicp_voxel_map",
+]
 # include/icp4r/icp4r_multi.h (the batched multi-GPU mode: shards, multi-device batch, RCCL gather)
 MULTI_EXPORTED_SYMBOLS = [
     "icp4r_shard", "icp4r_align_batch_multi", "icp4r_comm_unique_id", "icp4r_comm_create", "icp4r_comm_destroy",

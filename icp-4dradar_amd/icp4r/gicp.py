@@ -164,12 +164,16 @@ class FastGICPSingleThread:
         return self._p
 
     # --- Registration::align ---
+    def _align_call(self, guess):
+        """The registration behind align (icp4r.vgicp.FastVGICP has its own): (Result, aligned cloud)."""
+        return align(self._src, self._tgt, self._p, guess=guess, want_aligned=True, ctx=self._ctx)
+
     def align(self, output=None, guess=None) -> np.ndarray:
         if self._tgt is None or len(self._tgt) == 0:
             raise ICP4RError(E_EMPTY, "No input target dataset was given!")
         if self._src is None:
             raise ICP4RError(E_INVALID, "No input source dataset was given!")
-        r, aligned = align(self._src, self._tgt, self._p, guess=guess, want_aligned=True, ctx=self._ctx)
+        r, aligned = self._align_call(guess)
         self._result = r
         out = self._src.copy()
         out[:, :3] = aligned[:, :3]
