@@ -133,11 +133,13 @@ def lm_align(linearize, error, guess=None, max_iterations=64, rotation_epsilon=2
              lm_max_iterations=10, lm_init_lambda_factor=1e-9) -> dict:
     """LsqRegistration::align with step_lm.  linearize(R, t) -> (H 6x6, g 6, y, n_correspondences, kept);
     error(R, t, kept) -> y at another pose over the kept correspondences.
-    -> T (4x4 float64: x0), iterations (the index of the last iteration), converged, lm_failed, n_valid."""
+    -> T (4x4 float64: x0), iterations (the index of the last iteration), converged, lm_failed, n_valid;
+    a log beside them: trials (the trials evaluated per iteration) and stops (per iteration 1 accepted,
+    2 converged on a rejected trial, 0 every trial rejected)."""
     G = np.eye(4) if guess is None else np.asarray(guess, np.float32).astype(np.float64)
     R, t = G[:3, :3].copy(), G[:3, 3].copy()
     lam = -1.0
-    out = {"iterations": 0, "converged": False, "lm_failed": False, "n_valid": 0}
+    out = {"iterations": 0, "converged": False, "lm_failed": False, "n_valid": 0, "trials": [], "stops": []}
     with np.errstate(all="ignore"):
         for it in range(max_iterations):
             H, g, y0, n, kept = linearize(R, t)
@@ -146,7 +148,9 @@ def lm_align(linearize, error, guess=None, max_iterations=64, rotation_epsilon=2
             nu = 2.0
             stop = 0
             dR, dt = np.eye(3), np.zeros(3)
+            ntrials = 0
             for _ in range(lm_max_iterations):
+                ntrials += 1
                 d = ldlt_solve(H + lam * np.eye(6), -g)
                 dR, dt = so3_exp(d[:3]), d[3:].copy()
                 Rn, tn = dR @ R, dR @ t + dt
@@ -165,6 +169,8 @@ def lm_align(linearize, error, guess=None, max_iterations=64, rotation_epsilon=2
                     break
             out["iterations"] = it
             out["n_valid"] = int(n)
+            out["trials"].append(ntrials)
+            out["stops"].append(stop)
             if not stop:
                 out["lm_failed"] = True
                 break
